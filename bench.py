@@ -15,7 +15,12 @@ capped at 256 -> 256 / 256 / 128 / 64 at W = 1 / 2 / 4 / 8, global batch 256
 512 samples per rank instead (n = 512*W, per-rank batch 256) -- a config the
 reference never ran, kept as an extra.
 
-Usage: python bench.py --gpus N --steps K --warmup W
+Usage: python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up (W untimed steps), times K steps in one ``train(K)``
+call and prints the result line (``ms_per_step`` = the timed region / K);
+``--dump-outputs DIR`` also writes the state that call left (weights, optimizer
+moments, last step's losses; seeded, so identical inputs from run to run) as
+``DIR/<name>.npy``.  ``--full`` is where any further measurement belongs.
 N > 1 runs under an outer torchrun, or -- without one (no WORLD_SIZE in the
 environment) -- bench.py starts its own N ranks (``self_launch``).
 Prints ONE JSON line (rank 0's).
@@ -88,6 +93,13 @@ def parse():
                          "Driver-style K=20, 14 fresh processes each, interleaved: median 4.52 vs 4.62 us/step, and "
                          "no 8-10 us outliers (3 of 14 on the default stream; profiles/r6_misc/)")
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what train() left after its last step as DIR/<name>.npy "
+                         "(float32): params, opt_m, opt_v [2, P] and loss [2] (the last step's global mean losses)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every extra measurement of the benchmark.  A plain run already does only what "
+                         "the headline needs (set up, warm up, time --steps steps, print the line), so today "
+                         "--full adds nothing; an extra measurement added later goes behind it")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal only: every rank on cuda:(local_rank %% device_count), gloo process group "
                          "(exercises the multi-rank path on a 1-GPU box; numbers are not scaling numbers)")
@@ -149,6 +161,16 @@ def pin_host_thread(dev) -> int | None:
         return cpus[0]
     except (OSError, ValueError, AttributeError, IndexError):
         return None
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """``--dump-outputs``: each tensor as ``path/<name>.npy`` in float32 (the training state of
+    two models of a few hundred parameters each: a few KB in all)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to("cpu", torch.float32).contiguous().numpy())
 
 
 def _free_port() -> int:
@@ -369,11 +391,17 @@ def main():
     if a.impl == "native":
         runner.check_comm()  # raises if any in-kernel exchange of the run timed out
         final_loss = runner.losses(runner.t - 1, runner.t)[0].tolist()
+        if a.dump_outputs and rank == 0:  # every rank holds the same replica
+            dump_outputs(a.dump_outputs, {"params": runner.params, "opt_m": runner.m, "opt_v": runner.v,
+                                          "loss": torch.tensor(final_loss)})
         runner.close()  # process-group barrier before the xGMI buffers are unmapped
         if dbar is not None:
             dbar.close()
     else:
         final_loss = list(runner.last)
+        if a.dump_outputs and rank == 0:
+            flat = [torch.cat([p.detach().reshape(-1) for p in m.parameters()]) for m in (runner.mx, runner.my)]
+            dump_outputs(a.dump_outputs, {"params": torch.stack(flat), "loss": torch.tensor(final_loss)})
         runner.close()
 
     base = STOCK_SAMPLES_PER_S_1GPU * world

@@ -43,6 +43,37 @@ def test_bench_self_launch_fails_with_a_rank():
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
 
 
+def test_bench_dump_outputs_and_full_flag(tmp_path):
+    """--dump-outputs DIR writes the state the timed train() call left (float32 .npy), the
+    same from run to run (seeded inputs), its loss rows equal to the line's final_loss;
+    --steps is the number of timed steps (ms_per_step x steps = the timed region); --full
+    is accepted and leaves the headline fields as they are."""
+    import numpy as np
+
+    recs, outs = [], []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        d = tmp_path / name
+        r = _run(["--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", str(d), *extra])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        recs.append(json.loads(lines[0]))
+        outs.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    for rec, out in zip(recs, outs):
+        assert sorted(out) == ["loss", "opt_m", "opt_v", "params"]
+        assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in out.values())
+        assert out["params"].shape == out["opt_m"].shape == out["opt_v"].shape and out["params"].shape[0] == 2
+        assert out["loss"].tolist() == rec["final_loss"]
+        assert sum(v.nbytes for v in out.values()) <= 64 << 20
+        assert rec["steps"] == 4 and rec["ms_per_step"] > 0
+        assert abs(rec["value"] - 256 * 4 / (4 * rec["ms_per_step"] * 1e-3)) <= 1e-6 * rec["value"]
+        assert np.abs(out["opt_m"]).max() > 0  # steps were taken
+    for k in outs[0]:
+        assert np.array_equal(outs[0][k], outs[1][k]), k
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert recs[0][k] == recs[1][k]
+
+
 def test_bench_children_inherit_ipc_env():
     """The parent sets the collective environment before it launches the ranks: a rank
     finds HSA_ENABLE_IPC_MODE_LEGACY=0 at its own start, although the caller's

@@ -41,6 +41,50 @@ def test_bench_one_gpu_json_contract():
     assert rec["config"]["global_batch"] == 256 and rec["config"]["dataset_samples"] == 512
 
 
+def test_bench_dump_outputs_match_in_process_run(tmp_path):
+    """--dump-outputs: the weights, moments and last losses bench.py's timed path left are
+    those of the same 25 steps (5 warm-up + 20 timed) run in this process from the same
+    seed.  Same kernel instance, same step order, fp32 state stored between launches
+    without rounding: equal up to one fp32 ulp per element (rtol 2^-23, and the same
+    relative to the largest element for values near zero)."""
+    import numpy as np
+    import torch
+
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5",
+                        "--dump-outputs", str(tmp_path)], cwd=ROOT, capture_output=True, text=True, timeout=110)
+    assert r.returncode == 0, r.stderr[-2000:]
+    rec = _json_line(r.stdout)
+    got = {p.stem: np.load(p) for p in tmp_path.glob("*.npy")}
+    assert sorted(got) == ["loss", "opt_m", "opt_v", "params"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss"].tolist() == rec["final_loss"] and rec["steps"] == 20
+
+    sys.path.insert(0, ROOT)
+    from distributed_training_pytorch_amd.data.sampler import SamplerGeometry
+    from distributed_training_pytorch_amd.data.toy_data import ToyData
+    from distributed_training_pytorch_amd.engine.fused_trainer import EngineConfig, FusedTrainer
+    from distributed_training_pytorch_amd.models.toy import ToyModel
+    from distributed_training_pytorch_amd.ops.mlp import TOY_SPEC
+    from distributed_training_pytorch_amd.ops.optim import OptimConfig
+
+    dev = torch.device("cuda", 0)
+    X, Y = ToyData(n=512, seed=0).device_tensors(dev)
+    torch.manual_seed(0)
+    init = [ToyModel().flat_params.detach().clone() for _ in range(2)]
+    tr = FusedTrainer(TOY_SPEC, 2, X, Y, SamplerGeometry(n=512, batch=256, seed=0), OptimConfig(lr=1e-3),
+                      EngineConfig(), init_params=init)
+    tr.train(25)
+    tr.synchronize()
+    want = {"params": tr.params, "opt_m": tr.m, "opt_v": tr.v, "loss": tr.losses(24, 25)[0]}
+    want = {k: v.detach().cpu().numpy() for k, v in want.items()}
+    tr.close()
+    eps = 2.0 ** -23
+    for k, w in want.items():
+        print(k, "max abs diff", float(np.abs(got[k] - w).max()), "max abs", float(np.abs(w).max()))
+        assert got[k].shape == w.shape
+        assert np.all(np.abs(got[k] - w) <= eps * np.abs(w) + eps * np.abs(w).max()), k
+
+
 def _single_process_full_batch_losses(steps: int) -> list[float]:
     """The strong-scaling reference: at W >= 2 the 512-sample set is split over the W
     ranks with per-rank batch 512/W, so one step of the job sees every sample once --
