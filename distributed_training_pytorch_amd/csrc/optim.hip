@@ -138,7 +138,7 @@ __global__ __launch_bounds__(kBlock) void flat_optimizer_kernel(DtpOptArgs a) {
 }
 
 __global__ void advance_steps_kernel(int* step, int n) {
-  const int i = threadIdx.x;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) step[i] += 1;
 }
 
@@ -158,6 +158,9 @@ extern "C" int dtp_flat_optimizer(const DtpOptArgs* a, void* stream) {
   if (nblk > 1024) nblk = 1024;
   dim3 grid(nblk, a->n_models), block(dtp::kBlock);
   hipLaunchKernelGGL(dtp::flat_optimizer_kernel, grid, block, 0, st, *a);
-  if (nblk > 1) hipLaunchKernelGGL(dtp::advance_steps_kernel, dim3(1), dim3(64), 0, st, a->step, a->n_models);
+  // one thread per model: a single 64-thread block left the counters of models 64.. at
+  // their old step (those models then kept the first step's bias correction)
+  if (nblk > 1)
+    hipLaunchKernelGGL(dtp::advance_steps_kernel, dim3((a->n_models + 63) / 64), dim3(64), 0, st, a->step, a->n_models);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }

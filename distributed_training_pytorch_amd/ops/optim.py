@@ -78,6 +78,14 @@ def adam_bias_table(cfg: "OptimConfig", max_len: int = 1 << 22):
             e >>= 1
         return r
 
+    # beta ~ 1: the corrections are not yet 1.0 at the last step the search would reach
+    # (they only grow with t), so there is no table -- without forming max_len rows to see it
+    n = 1024
+    while n < max_len:
+        n *= 2
+    last = np.array([n - 1], dtype=np.int64)
+    if not ((1.0 - pow_int(b1, last) == 1.0) & (1.0 - pow_int(b2, last) == 1.0)).all():
+        return None
     n = 1024
     while True:
         t = np.arange(n, dtype=np.int64)

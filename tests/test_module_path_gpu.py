@@ -47,24 +47,37 @@ def test_forward_many_matches_separate_fused_calls(freeze_second):
                 assert torch.equal(p.grad, q.grad)
 
 
-def _train_flat(fuse: bool, opt_name: str, steps: int = 6, batch: int = 200):
+def _flat_cfgs():
+    from distributed_training_pytorch_amd.ops.optim import OptimConfig
+
+    return {"adam": OptimConfig("adam", lr=1e-2), "sgd": OptimConfig("sgd", lr=1e-2, momentum=0.9),
+            "all": OptimConfig("adam", lr=1e-2, betas=(0.8, 0.95), eps=1e-4, weight_decay=1e-2),
+            "sgd_wd": OptimConfig("sgd", 5e-2, momentum=0.9, weight_decay=1e-2)}
+
+
+def _train_flat(fuse: bool, cfg, steps: int = 6, batch: int = 200, record: dict | None = None):
+    """record: filled with the initial flat parameters and every (x, y) batch (CPU copies),
+    for a reference run of the same loop."""
     import contextlib
 
     from distributed_training_pytorch_amd.ops.loss import mse_loss
     from distributed_training_pytorch_amd.ops.mlp import ParamBackwardFusion
-    from distributed_training_pytorch_amd.ops.optim import FlatOptimizer, OptimConfig
+    from distributed_training_pytorch_amd.ops.optim import FlatOptimizer
     from distributed_training_pytorch_amd.parallel.ddp import FlatDDP
 
     torch.manual_seed(5)
     m = ToyModel().cuda()
     ddp = FlatDDP(m)
-    cfg = OptimConfig(name=opt_name, lr=1e-2, momentum=0.9 if opt_name == "sgd" else 0.0)
     opt = FlatOptimizer(ddp.flat_params, ddp.flat_grad, cfg)
     g = torch.Generator(device="cuda").manual_seed(1)
     taken = 0
+    if record is not None:
+        record.update(init=ddp.flat_params.detach().cpu().clone(), xy=[])
     for _ in range(steps):
         x = torch.randn(batch, 2, device="cuda", generator=g)
         y = torch.randn(batch, 1, device="cuda", generator=g)
+        if record is not None:
+            record["xy"].append((x.cpu(), y.cpu()))
         ddp.zero_grad()
         with (ParamBackwardFusion() if fuse else contextlib.nullcontext()) as fus:
             mse_loss(ddp(x), y).backward()
@@ -76,21 +89,48 @@ def _train_flat(fuse: bool, opt_name: str, steps: int = 6, batch: int = 200):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("opt_name", ["adam", "sgd"])
+@pytest.mark.parametrize("opt_name", ["adam", "sgd", "all", "sgd_wd"])
 def test_stage_backward_fused_with_flat_optimizer_is_bitwise_the_pair(opt_name):
     """ParamBackwardFusion: the model's stage backward (adding into its persistent flat
     gradient) and the flat optimizer step over that span in ONE launch
     (``mlp_stage_bwd_opt_kernel``) leave parameters, moments, step counter and the
-    (zeroed) gradient bitwise where the two separate launches leave them."""
+    (zeroed) gradient bitwise where the two separate launches leave them -- with the
+    default hyperparameters and with betas, eps and weight decay set ("all", "sgd_wd").
+    Two wrong kernels can agree bitwise, so "all" is also held against the same loop in
+    fp64 (a double nn.Sequential twin under torch.optim.Adam on the same batches), which
+    itself must tell "all" from the default Adam by far more than the tolerance."""
     from distributed_training_pytorch_amd import _native as nat
 
     nat.require(torch.device("cuda", 0))
-    ref, n0 = _train_flat(False, opt_name)
-    got, n1 = _train_flat(True, opt_name)
+    cfg = _flat_cfgs()[opt_name]
+    rec = {}
+    ref, n0 = _train_flat(False, cfg)
+    got, n1 = _train_flat(True, cfg, record=rec)
     assert n0 == 0 and n1 == 6  # every step fused
     for a, b in zip(ref, got):
         assert torch.equal(a, b)
     assert int(got[3][0]) == 6 and not got[4].any()
+    if opt_name == "all":
+        rtol, atol = 1e-4, 2e-5
+        want = _train_flat_fp64(cfg, rec)
+        plain = _train_flat_fp64(_flat_cfgs()["adam"], rec)
+        far = (want - plain).abs() > 10 * (atol + rtol * plain.abs())
+        assert far.double().mean() >= 0.5, far.double().mean()
+        torch.testing.assert_close(got[0].cpu().double().view(-1), want, rtol=rtol, atol=atol)
+
+
+def _train_flat_fp64(cfg, record):
+    """_train_flat's loop on a double twin of the model: autograd + torch.optim."""
+    import copy
+
+    twin = copy.deepcopy(ToyModel().layers).double()
+    torch.nn.utils.vector_to_parameters(record["init"].double().view(-1), twin.parameters())
+    opt = cfg.torch_optimizer(twin.parameters())
+    for x, y in record["xy"]:
+        opt.zero_grad()
+        torch.nn.functional.mse_loss(twin(x.double()), y.double()).backward()
+        opt.step()
+    return torch.nn.utils.parameters_to_vector(twin.parameters()).detach()
 
 
 def _fit_lit(root, copies, graphs=True, steps=23, batch=96):
