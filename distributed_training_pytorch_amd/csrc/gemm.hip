@@ -538,7 +538,10 @@ __global__ __launch_bounds__(256) void gemm_skinny_k_kernel(DtpGemmArgs a) {
   for (int c = 0; c < 8; ++c) bias[c] = (a.bias && n0 + cc + c < a.N) ? a.bias[n0 + cc + c] : 0.f;
   char* C = static_cast<char*>(a.C);
   const char* aux = static_cast<const char*>(a.aux);
-  const bool vec_c = (a.ldc % 8 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) && n0 + cc + 8 <= a.N;
+  // the vector branch moves C and a bf16 aux as 16-byte rows: both need aligned rows
+  // (an f32-operand aux is loaded per element)
+  const bool vec_aux = DT != DTP_DT_BF16 || !aux || (a.ldaux % 8 == 0 && (reinterpret_cast<uintptr_t>(aux) & 15) == 0);
+  const bool vec_c = (a.ldc % 8 == 0) && ((reinterpret_cast<uintptr_t>(C) & 15) == 0) && vec_aux && n0 + cc + 8 <= a.N;
   float breg[8][KC > 0 ? KC : 1];
   if constexpr (KC > 0) {
 #pragma unroll
@@ -565,9 +568,9 @@ __global__ __launch_bounds__(256) void gemm_skinny_k_kernel(DtpGemmArgs a) {
     }
     if (vec_c && a.out_dtype == DTP_DT_BF16 && !a.accumulate) {
       if (aux) {
-        const uint4 g = *reinterpret_cast<const uint4*>(aux + ((long long)m * a.ldaux + n0 + cc) * ES);
         float gv[8];
         if constexpr (DT == DTP_DT_BF16) {
+          const uint4 g = *reinterpret_cast<const uint4*>(aux + ((long long)m * a.ldaux + n0 + cc) * ES);
           const uint32_t w[4] = {g.x, g.y, g.z, g.w};
 #pragma unroll
           for (int q = 0; q < 4; ++q) {

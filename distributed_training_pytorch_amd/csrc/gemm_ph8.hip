@@ -396,6 +396,7 @@ __global__ __launch_bounds__(kThreads) void gemm_ph8_kernel(DtpGemmArgs a) {
     e.act = 0;
     e.accumulate = 0;
     e.alpha = 1.f;
+    e.splitk = 1;  // plain stores on the per-element path too: the workspace is uninitialised, not an atomic target
     store(e);
   } else {
     store(a);
