@@ -30,6 +30,12 @@ def build_parser(description: str | None = None) -> argparse.ArgumentParser:
     p.add_argument("--optimizer", choices=["adam", "sgd"], default="adam")
     p.add_argument("--momentum", type=float, default=0.0)
     p.add_argument("--weight_decay", type=float, default=0.0)
+    clip = p.add_mutually_exclusive_group()
+    clip.add_argument("--clip_grad_norm", type=float, default=0.0,
+                      help="> 0: clip each model's gradient to this L2 norm before its optimizer step "
+                           "(torch.nn.utils.clip_grad_norm_ per optimizer; the module engine's flat kernel does it)")
+    clip.add_argument("--clip_grad_value", type=float, default=0.0,
+                      help="> 0: clamp every gradient element to [-F, F] before the optimizer step")
     p.add_argument("--loss", choices=["mse", "ce"], default="mse")
     p.add_argument("--n_samples", type=int, default=512, help="ToyData size (toy_model_and_data.py:29)")
     p.add_argument("--per_rank_data", action="store_true",

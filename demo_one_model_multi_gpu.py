@@ -107,6 +107,10 @@ def _ckpt_due(config, it):
 @record
 def main(argv=None):
     config = get_args(argv)
+    if config.clip_grad_norm > 0 or config.clip_grad_value > 0:
+        # a model's norm would span the stages on several GPUs: not built here
+        raise SystemExit("demo_one_model_multi_gpu.py: --clip_grad_norm / --clip_grad_value are not supported with "
+                         "a layer-split model (the gradient norm would span the stages' GPUs); use demo.py")
     if config.dry_run:
         os.environ["WANDB_MODE"] = "dryrun"
     K = config.gpus_per_proc

@@ -83,6 +83,11 @@ def get_args(argv=None):
                    help="resume: a checkpoint file, or 'last' for the newest one under <root_dir>/lightning_logs")
     p.add_argument("--every_n_train_steps", type=int, default=0,
                    help="also save lightning_logs/version_N/checkpoints/last.ckpt every N batches")
+    clip = p.add_mutually_exclusive_group()
+    clip.add_argument("--clip_grad_norm", type=float, default=0.0,
+                      help="Trainer(gradient_clip_val=F, gradient_clip_algorithm='norm'): per optimizer, before its step")
+    clip.add_argument("--clip_grad_value", type=float, default=0.0,
+                      help="Trainer(gradient_clip_val=F, gradient_clip_algorithm='value')")
     return p.parse_args(argv)
 
 
@@ -108,6 +113,9 @@ def main(argv=None):
     extra = {"seed": a.seed, "use_graphs": not a.no_graphs, "native_optimizers": not a.torch_optimizers,
              "every_n_train_steps": a.every_n_train_steps, "engine": engine} if TrainerCls is Trainer else {}
     precision = 32 if a.precision == "32" else "bf16"
+    if a.clip_grad_norm > 0 or a.clip_grad_value > 0:  # Lightning's own Trainer takes the same two arguments
+        extra.update(gradient_clip_val=a.clip_grad_norm or a.clip_grad_value,
+                     gradient_clip_algorithm="norm" if a.clip_grad_norm > 0 else "value")
     trainer = TrainerCls(gpus=a.gpus, num_nodes=a.nnodes, max_steps=a.steps, precision=precision, accelerator=accel,
                          log_every_n_steps=min(50, len(dl) / a.batch_size), strategy="ddp",
                          default_root_dir=a.root_dir, enable_progress_bar=not a.no_progress, **extra)

@@ -185,6 +185,10 @@ class OptArgs(ctypes.Structure):
         ("hp", Hyper),
         ("shadow", c_void_p),
         ("shadow_ld", c_longlong),
+        ("max_norm", c_float),
+        ("clip_value", c_float),
+        ("norm_ws", c_void_p),
+        ("norm_out", c_void_p),
     ]
 
 
@@ -259,6 +263,9 @@ def _declare(lib):
         "dtp_mlp_stage_fwd_multi": (c_int, [P(StageMulti), c_int, c_int, c_int, c_int, c_int, c_void_p]),
         "dtp_mlp_stage_bwd": (c_int, [P(StageArgs), c_int, c_int, c_int, c_int, c_int, c_void_p]),
         "dtp_flat_optimizer": (c_int, [P(OptArgs), c_void_p]),
+        "dtp_grad_norm": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+        "dtp_grad_norm_ws_bytes": (c_longlong, [c_int]),
+        "dtp_clip_grad_norm": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
         "dtp_mlp_stage_bwd_opt": (c_int, [P(StageMulti), P(OptArgs), c_int, c_int, c_int, c_int, c_int, c_void_p]),
         "dtp_mse_max_elems": (c_longlong, []),
         "dtp_mse_fwd": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p]),

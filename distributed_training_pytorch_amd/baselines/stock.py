@@ -22,8 +22,12 @@ def plain_toy_model(slope: float = 0.01) -> nn.Module:
 
 
 class StockLoop:
-    def __init__(self, dataset, device, batch: int = 256, seed: int = 0, ddp: bool = True):
+    def __init__(self, dataset, device, batch: int = 256, seed: int = 0, ddp: bool = True,
+                 clip_grad_norm: float = 0.0, clip_grad_value: float = 0.0):
         torch.manual_seed(seed)
+        # gradient clipping per model (= per optimizer), torch's own functions; 0 = off
+        self.clip_grad_norm = clip_grad_norm
+        self.clip_grad_value = clip_grad_value
         self.device = device
         self.mx = plain_toy_model().to(device)
         self.my = plain_toy_model().to(device)
@@ -69,6 +73,11 @@ class StockLoop:
         lx.backward()
         ly = self.loss(out_y, target)
         ly.backward()
+        for m in (self.mx, self.my):
+            if self.clip_grad_norm > 0:
+                torch.nn.utils.clip_grad_norm_(m.parameters(), self.clip_grad_norm)
+            elif self.clip_grad_value > 0:
+                torch.nn.utils.clip_grad_value_(m.parameters(), self.clip_grad_value)
         self.ox.step()
         self.oy.step()
         b = target.size(0)

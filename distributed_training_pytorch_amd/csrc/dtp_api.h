@@ -178,10 +178,22 @@ struct DtpOptArgs {
   DtpHyper hp;
   void* shadow;       // [n_models][shadow_ld] bf16 copy of the updated params, or null
   long long shadow_ld;  // row stride of shadow in elements (>= P)
+  // gradient clipping, per row (one model = one optimizer); all zeros = off.  At most one of
+  // max_norm / clip_value may be set.
+  float max_norm;     // > 0: scale row i's gradient by clamp(max_norm / (norm_i + 1e-6), max=1)
+  float clip_value;   // > 0: clamp every element of grad * hp.grad_scale to [-clip_value, clip_value]
+  double* norm_ws;    // max_norm > 0 and P > 4096: dtp_grad_norm_ws_bytes(P) * n_models bytes of scratch
+  float* norm_out;    // max_norm > 0: [n_models] L2 norm of grad * hp.grad_scale before clipping
 };
 
 #define DTP_OPT_ZERO_GRAD 1
 int dtp_flat_optimizer(const DtpOptArgs* a, void* stream);
+// out[i] = || grad[i, :] * scale ||_2 (fp64 accumulation in a fixed order: bitwise reproducible);
+// ws: dtp_grad_norm_ws_bytes(P) * n_models bytes (may be null when that is 0)
+int dtp_grad_norm(const float* grad, int n_models, int P, float scale, double* ws, float* out, void* stream);
+long long dtp_grad_norm_ws_bytes(int P);
+// the same norm, then grad[i, :] *= clamp(max_norm / (out[i] + 1e-6), max=1) in place: two launches
+int dtp_clip_grad_norm(float* grad, int n_models, int P, float max_norm, double* ws, float* out, void* stream);
 
 // ---- MFMA GEMM with fused Linear epilogues (gemm.hip) ----
 #define DTP_DT_F32 0

@@ -270,6 +270,9 @@ extern "C" {
 int dtp_mlp_stage_bwd_opt(const DtpStageMulti* m, const DtpOptArgs* o, int in, int h, int nl, int out, int final_act,
                           void* stream) {
   if (!m || !o) return set_err(-1, "stage_bwd_opt: null arguments");
+  // the backward is still writing the gradient: its norm cannot be formed in the same launch
+  if (o->max_norm != 0.f || o->clip_value != 0.f)
+    return set_err(-6, "stage_bwd_opt: gradient clipping needs the backward launched before the optimizer step");
   hipStream_t st = (hipStream_t)stream;
 #define X(I, H, N, O, F) \
   if (in == I && h == H && nl == N && out == O && (bool)final_act == F) return launch_stage_bwd_opt<dtp::Stage<I, H, N, O, F>>(m, o, st);

@@ -92,6 +92,20 @@ DTP_DEV void adam_update(float& p, float& m, float& v, float g, const AdamScalar
 #endif
 }
 
+// torch.nn.utils.clip_grad_norm_'s coefficient from the fp32 total norm, operation for
+// operation: clip_coef = max_norm / (total_norm + 1e-6) is Tensor.__rtruediv__, i.e.
+// (total_norm + 1e-6).reciprocal() * max_norm, then clamp(max=1.0).  Correctly rounded
+// division (not div_nr): the coefficient is bitwise torch's.  A NaN norm gives a NaN
+// coefficient and an infinite one 0, as torch with error_if_nonfinite=False.
+DTP_DEV float clip_coef(float norm, float max_norm) {
+  const float r = 1.0f / (norm + 1e-6f);
+  const float c = r * max_norm;
+  return c > 1.0f ? 1.0f : c;
+}
+
+// torch.nn.utils.clip_grad_value_: g.clamp_(-c, c); NaN stays NaN
+DTP_DEV float clamp_value(float g, float c) { return g < -c ? -c : (g > c ? c : g); }
+
 DTP_DEV void sgd_update(float& p, float& buf, float g, float lr, float mom, float wd, bool first) {
   if (wd != 0.f) g = fmaf(wd, p, g);
   if (mom != 0.f) {

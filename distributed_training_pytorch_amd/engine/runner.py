@@ -105,7 +105,16 @@ def _fused_supported(config) -> bool:
 
 
 def _optim(config) -> OptimConfig:
-    return OptimConfig(config.optimizer, config.lr, momentum=config.momentum, weight_decay=config.weight_decay)
+    return OptimConfig(config.optimizer, config.lr, momentum=config.momentum, weight_decay=config.weight_decay,
+                       max_grad_norm=_clip_norm(config), clip_grad_value=_clip_value(config))
+
+
+def _clip_norm(config) -> float:
+    return max(float(getattr(config, "clip_grad_norm", 0.0) or 0.0), 0.0)
+
+
+def _clip_value(config) -> float:
+    return max(float(getattr(config, "clip_grad_value", 0.0) or 0.0), 0.0)
 
 
 def _progress(rank, total, config):
@@ -130,6 +139,11 @@ def train(config, env, device, rank, world, group: str = "base-demo") -> dict:
         # nn.Modules whose Linears run on the MFMA GEMM (FlatDDP + FlatOptimizer)
         rank_print(rank, f"fused step kernel has no instance for hidden={config.hidden} depth={config.depth} "
                          f"precision={config.precision}: using the module engine (MFMA GEMM layers)")
+        engine = "module"
+    if engine == "fused" and (_clip_norm(config) > 0 or _clip_value(config) > 0):
+        # the fused persistent step has no clipping: the module engine's flat optimizer kernel does it
+        rank_print(rank, "gradient clipping (--clip_grad_norm / --clip_grad_value) is not in the fused step "
+                         "kernel: using the module engine")
         engine = "module"
     if engine == "fused":
         summary = _train_fused(config, device, rank, world, logger, faults)
@@ -434,6 +448,8 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
             "samples_per_s": geom.batch * (config.iters - start) * world / max(dt, 1e-9),
             "steady_samples_per_s": steady, "engine": "module",
             "graph_replays": stepper.replays,
+            # clipping by norm: each model's gradient norm at the last step, before clipping
+            **({"grad_norm": opt.grad_norm.tolist()} if _clip_norm(config) > 0 else {}),
             **({"phases": timer.summary()} if trace_enabled() else {})}
 
 
@@ -456,7 +472,8 @@ def _train_stock(config, device, rank, world, logger, faults) -> dict:
     from ..baselines.stock import StockLoop
 
     ds = _dataset(config, rank)
-    loop = StockLoop(ds, device, batch=config.batch_size, seed=config.seed)
+    loop = StockLoop(ds, device, batch=config.batch_size, seed=config.seed,
+                     clip_grad_norm=_clip_norm(config), clip_grad_value=_clip_value(config))
     pbar = _progress(rank, config.iters, config)
     timer = PhaseTimer(device)
     t0 = time.perf_counter()

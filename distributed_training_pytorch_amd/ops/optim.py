@@ -23,6 +23,17 @@ class OptimConfig:
     eps: float = 1e-8
     weight_decay: float = 0.0
     momentum: float = 0.0
+    # gradient clipping, per row (one model = one optimizer); 0 = off, at most one of them:
+    max_grad_norm: float = 0.0    # > 0: torch.nn.utils.clip_grad_norm_(row, max_grad_norm)
+    clip_grad_value: float = 0.0  # > 0: torch.nn.utils.clip_grad_value_(row, clip_grad_value)
+
+    def __post_init__(self):
+        if self.max_grad_norm > 0 and self.clip_grad_value > 0:
+            raise ValueError("OptimConfig: max_grad_norm and clip_grad_value are exclusive (one clipping algorithm)")
+
+    @property
+    def clips(self) -> bool:
+        return self.max_grad_norm > 0 or self.clip_grad_value > 0
 
     @property
     def kind(self) -> int:
@@ -116,9 +127,83 @@ def sgd_update_ref(p: torch.Tensor, buf: torch.Tensor, g: torch.Tensor, first: b
     p.add_(g, alpha=-cfg.lr)
 
 
+def grad_norm_ws(P: int, n_models: int, device) -> torch.Tensor | None:
+    """The scratch ``grad_norm`` / a clipped step needs for [n_models, P] rows on ``device``
+    (fp64 per-block partials; None where one block per row does it all)."""
+    device = torch.device(device)
+    if device.type != "cuda" or not nat.native_enabled():
+        return None
+    nbytes = int(nat.require(device).dtp_grad_norm_ws_bytes(P))
+    return torch.empty(n_models * nbytes // 8, dtype=torch.float64, device=device) if nbytes else None
+
+
+def _rows(flat_grad: torch.Tensor) -> torch.Tensor:
+    g = flat_grad if flat_grad.dim() == 2 else flat_grad.view(1, -1)
+    if g.dtype != torch.float32 or not g.is_contiguous():
+        raise ValueError("expected a contiguous float32 [n_models, P] (or [P]) gradient")
+    return g
+
+
+def _norm_ref(g: torch.Tensor) -> torch.Tensor:
+    """Per-row L2 norm, accumulated in float64 and rounded to float32 (what the kernel forms)."""
+    return g.double().square().sum(dim=1).sqrt().float()
+
+
+def _clip_coef_ref(norm: torch.Tensor, max_norm: float) -> torch.Tensor:
+    """torch.nn.utils.clip_grad_norm_'s coefficient, its own expression."""
+    return (float(max_norm) / (norm + 1e-6)).clamp(max=1.0)
+
+
+@torch.no_grad()
+def grad_norm(flat_grad: torch.Tensor, scale: float = 1.0, out: torch.Tensor | None = None,
+              ws: torch.Tensor | None = None) -> torch.Tensor:
+    """L2 norm of every row of ``flat_grad * scale`` ([n_models, P] or [P]) -> float32 [n].
+
+    fp64 accumulation in a fixed order: bitwise reproducible, no host sync.  ``out`` / ``ws``
+    (``grad_norm_ws``): preallocated result and scratch, for calls under graph capture."""
+    g = _rows(flat_grad)
+    n, P = g.shape
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=g.device)
+    if g.is_cuda and nat.native_enabled():
+        lib = nat.require(g.device)
+        if ws is None:
+            ws = grad_norm_ws(P, n, g.device)
+        nat.check(lib.dtp_grad_norm(nat.ptr(g), n, P, scale, nat.ptr(ws), nat.ptr(out), nat.stream_ptr()),
+                  "dtp_grad_norm")
+        return out
+    out.copy_(_norm_ref(g * scale))
+    return out
+
+
+@torch.no_grad()
+def clip_grad_norm_(flat_grad: torch.Tensor, max_norm: float, out: torch.Tensor | None = None,
+                    ws: torch.Tensor | None = None) -> torch.Tensor:
+    """``torch.nn.utils.clip_grad_norm_`` per row of a flat [n_models, P] (or [P]) gradient,
+    in place; returns the norms before clipping (float32 [n]).  The norm launch and one
+    scale launch (one launch in all for rows of up to 4096 elements): for users who keep a
+    torch optimizer over ``FlatDDP.flat_grad``; ``FlatOptimizer`` clips inside its step."""
+    if not max_norm > 0:
+        raise ValueError("clip_grad_norm_: max_norm must be > 0")
+    g = _rows(flat_grad)
+    n, P = g.shape
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=g.device)
+    if g.is_cuda and nat.native_enabled():
+        lib = nat.require(g.device)
+        if ws is None:
+            ws = grad_norm_ws(P, n, g.device)
+        nat.check(lib.dtp_clip_grad_norm(nat.ptr(g), n, P, max_norm, nat.ptr(ws), nat.ptr(out), nat.stream_ptr()),
+                  "dtp_clip_grad_norm")
+        return out
+    out.copy_(_norm_ref(g))
+    g.mul_(_clip_coef_ref(out, max_norm).unsqueeze(1))
+    return out
+
+
 def flat_optimizer_step(params, m, v, step, grad, cfg: OptimConfig, grad_scale: float = 1.0,
                         loss_log=None, loss_scale: float = 1.0, slope: float = 0.01, shadow=None,
-                        zero_grad: bool = False, fused=None) -> None:
+                        zero_grad: bool = False, fused=None, norm_out=None, norm_ws=None) -> None:
     """One optimizer step over [n_models, P] flat buffers.
 
     ``grad`` is [n_models*P (+ n_models losses)] -- the all-reduced comm buffer;
@@ -128,17 +213,38 @@ def flat_optimizer_step(params, m, v, step, grad, cfg: OptimConfig, grad_scale: 
     rows are zeroed in the same pass once read (the loss slots are not).  ``fused``: a
     deferred stage backward (``ops.mlp.ParamBackwardFusion``) whose span is exactly this
     optimizer's rows (row i = stage i): the backwards and this step run as one launch.
+
+    Clipping (``cfg.max_grad_norm`` / ``cfg.clip_grad_value``) applies per row to
+    ``grad * grad_scale``, the averaged gradient torch would see, inside the same launch
+    (rows of more than 4096 elements: one norm launch first).  ``norm_out`` (float32
+    [n_models]) receives each row's norm before clipping; ``norm_ws``: ``grad_norm_ws``.
+    Both are allocated here when missing -- pass them for a step under graph capture.  A
+    clipped step launches ``fused`` backwards first: the norm needs the finished gradient.
     """
     n_models, P = params.shape
+    if cfg.max_grad_norm > 0 and cfg.clip_grad_value > 0:
+        raise ValueError("flat_optimizer_step: max_grad_norm and clip_grad_value are exclusive")
+    by_norm = cfg.max_grad_norm > 0
     if shadow is not None and (shadow.dtype != torch.bfloat16 or shadow.dim() != 2 or shadow.shape[0] != n_models
                                or shadow.shape[1] < P or shadow.stride(1) != 1 or shadow.device != params.device):
         raise ValueError("flat_optimizer_step: shadow must be a bf16 [n_models, >= P] tensor with unit column stride")
     if params.is_cuda and nat.native_enabled():
         lib = nat.require(params.device)
+        if by_norm:
+            if norm_out is None:
+                norm_out = torch.empty(n_models, dtype=torch.float32, device=params.device)
+            if norm_ws is None:
+                norm_ws = grad_norm_ws(P, n_models, params.device)
         a = nat.OptArgs(nat.ptr(params), nat.ptr(m), nat.ptr(v), nat.ptr(step), nat.ptr(grad),
                         nat.ptr(loss_log), 0 if loss_log is None else loss_log.shape[0], n_models, P, cfg.kind,
                         loss_scale, 1 if zero_grad else 0, cfg.hyper(slope, grad_scale), nat.ptr(shadow),
-                        0 if shadow is None else shadow.stride(0))
+                        0 if shadow is None else shadow.stride(0), max(cfg.max_grad_norm, 0.0),
+                        max(cfg.clip_grad_value, 0.0), nat.ptr(norm_ws) if by_norm else None,
+                        nat.ptr(norm_out) if by_norm else None)
+        if fused is not None and cfg.clips:
+            for p in fused:
+                p.launch()
+            fused = None
         if fused is not None:  # the stage backwards that produced `grad`, in the same launch
             from .mlp import launch_fused_with_optimizer
 
@@ -150,6 +256,13 @@ def flat_optimizer_step(params, m, v, step, grad, cfg: OptimConfig, grad_scale: 
         for p in fused:
             p.launch()
     g = grad[: n_models * P].view(n_models, P) * grad_scale
+    if by_norm:
+        norm = _norm_ref(g)
+        if norm_out is not None:
+            norm_out.copy_(norm)
+        g = g * _clip_coef_ref(norm, cfg.max_grad_norm).unsqueeze(1)
+    elif cfg.clip_grad_value > 0:
+        g = g.clamp(min=-cfg.clip_grad_value, max=cfg.clip_grad_value)
     for i in range(n_models):
         t = int(step[i])
         if cfg.name == "adam":
@@ -167,7 +280,12 @@ def flat_optimizer_step(params, m, v, step, grad, cfg: OptimConfig, grad_scale: 
 
 class FlatOptimizer:
     """Adam/SGD over flat [n_models, P] (or [P]) params + grads in one kernel launch
-    (replaces the reference's two torch.optim.Adam, each ~7 kernels x 10 tensors)."""
+    (replaces the reference's two torch.optim.Adam, each ~7 kernels x 10 tensors).
+
+    ``cfg.max_grad_norm`` / ``cfg.clip_grad_value`` clip every row's gradient inside the
+    same launch (one norm launch more for rows of over 4096 elements); ``grad_norm``
+    (float32 [n_models], device) then holds each row's norm before clipping, as
+    ``torch.nn.utils.clip_grad_norm_`` returns it, after every step -- no host sync."""
 
     def __init__(self, flat_params: torch.Tensor, flat_grad: torch.Tensor, cfg: OptimConfig | None = None,
                  slope: float = 0.01, shadow=None):
@@ -186,6 +304,9 @@ class FlatOptimizer:
         self._buf = None if self.grad.is_contiguous() else \
             torch.zeros(n * P + n, dtype=self.params.dtype, device=self.params.device)
         self.slope = slope
+        # clipping by norm: the result and the scratch are made here, never during a capture
+        self.grad_norm = torch.zeros(n, dtype=torch.float32, device=self.params.device)
+        self._norm_ws = grad_norm_ws(P, n, self.params.device) if self.cfg.max_grad_norm > 0 else None
 
     @torch.no_grad()
     def step(self, zero_grad: bool = False, fused=None) -> bool:
@@ -202,7 +323,7 @@ class FlatOptimizer:
         if fused is not None:
             from .mlp import fused_rows_match
 
-            if fresh or not fused_rows_match(fused, self.params, self.grad):
+            if fresh or self.cfg.clips or not fused_rows_match(fused, self.params, self.grad):
                 for p in fused:
                     p.launch()
                 fused = None
@@ -213,7 +334,8 @@ class FlatOptimizer:
             buf = self._buf
             zero_grad = False
         flat_optimizer_step(self.params, self.m, self.v, self.step_ctr, buf, self.cfg, slope=self.slope,
-                            shadow=sh.buf if fresh else None, zero_grad=zero_grad, fused=fused)
+                            shadow=sh.buf if fresh else None, zero_grad=zero_grad, fused=fused,
+                            norm_out=self.grad_norm, norm_ws=self._norm_ws)
         if fresh:
             sh.mark_fresh()
         return zero_grad

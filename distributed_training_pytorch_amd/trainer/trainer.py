@@ -21,6 +21,7 @@ MI355X-first: a dataset exposing device tensors (``ToyData``) is gathered on the
 from __future__ import annotations
 
 import contextlib
+import dataclasses
 import ctypes
 import csv
 import datetime
@@ -310,7 +311,8 @@ class Trainer:
                  log_every_n_steps: float = 50, default_root_dir: str | None = None,
                  enable_checkpointing: bool = True, enable_progress_bar: bool = True, seed: int | None = None,
                  use_graphs: bool = True, native_optimizers: bool = True, every_n_train_steps: int = 0,
-                 engine: str = "auto", graph_copies: int | None = None, **unused):
+                 engine: str = "auto", graph_copies: int | None = None, gradient_clip_val: float | None = None,
+                 gradient_clip_algorithm: str = "norm", **unused):
         if precision in (32, "32", "32-true"):
             self.autocast_dtype = None
         elif precision in ("bf16", "bf16-mixed"):
@@ -319,6 +321,14 @@ class Trainer:
         else:
             raise NotImplementedError(f"precision={precision!r}: supported are 32 and 'bf16'")
         self.precision = precision
+        # PL 1.5: clip each optimizer's gradients after its backward (and the all-reduce),
+        # before its step; None or 0 = off.  "norm": clip_grad_norm_, "value": clip_grad_value_
+        if gradient_clip_algorithm not in ("norm", "value"):
+            raise ValueError(f"gradient_clip_algorithm={gradient_clip_algorithm!r}: 'norm' or 'value'")
+        self.gradient_clip_val = float(gradient_clip_val or 0.0)
+        if self.gradient_clip_val < 0:
+            raise ValueError(f"gradient_clip_val={gradient_clip_val!r}: must be >= 0")
+        self.gradient_clip_algorithm = gradient_clip_algorithm
         self.gpus = gpus
         self.num_nodes = num_nodes
         self.max_steps = -1 if max_steps is None else int(max_steps)  # PL 1.5: None = unbounded
@@ -427,7 +437,8 @@ class Trainer:
             p.dtype == torch.float32 and p.device == self.device for p in model.parameters() if p.requires_grad)
         ddp = FlatDDP(model) if (self.world_size > 1 or single_ok) else None
         loader = self._loader(dl)
-        self._flat_opts = [_flat_optimizer_for(o, ddp) if self.native_optimizers else None for o in opts]
+        self._flat_opts = [_flat_optimizer_for(o, ddp, self._clip_fields()) if self.native_optimizers else None
+                           for o in opts]
         # every trainable parameter under exactly one flat optimizer (one optimizer, or
         # several toggled per PL 1.5 so a backward touches only the stepping optimizer's
         # gradients): each flat step leaves the whole flat gradient zero
@@ -580,6 +591,15 @@ class Trainer:
         def no(why):
             if self.engine == "fused":
                 raise RuntimeError(f"Trainer(engine='fused'): {why}")
+            return None
+
+        if self.gradient_clip_val > 0:
+            # the fused engine has no clipping: the module path's flat optimizer kernel does it
+            why = f"gradient clipping (gradient_clip_val={self.gradient_clip_val:g}) is not in the fused engine"
+            no(why)
+            if self.global_rank == 0:
+                rank_print(0, f"Trainer: not using the fused engine ({why}); per-batch module path")
+            self.fused_refused = why
             return None
 
         fs = getattr(model, "fused_spec", None)
@@ -916,10 +936,29 @@ class Trainer:
                             and ddp is not None:
                         ddp.mark_grad_clean()
                 else:
+                    self._clip_torch(opt)
                     opt.step()
             if len(opts) > 1:
                 model.untoggle_optimizer(oi)
             model._logged[f"train_loss_opt{oi}"] = loss.detach()
+
+    def _clip_fields(self) -> dict:
+        """The Trainer's clipping as OptimConfig fields (the flat optimizer kernel clips)."""
+        if self.gradient_clip_val <= 0:
+            return {}
+        key = "max_grad_norm" if self.gradient_clip_algorithm == "norm" else "clip_grad_value"
+        return {key: self.gradient_clip_val}
+
+    def _clip_torch(self, opt) -> None:
+        """Where torch's own step runs (CPU, optimizers outside the flat kernel's domain):
+        torch's clipping over that optimizer's parameters, before its step."""
+        if self.gradient_clip_val <= 0:
+            return
+        params = [p for g in opt.param_groups for p in g["params"] if p.grad is not None]
+        if self.gradient_clip_algorithm == "norm":
+            torch.nn.utils.clip_grad_norm_(params, self.gradient_clip_val)
+        else:
+            torch.nn.utils.clip_grad_value_(params, self.gradient_clip_val)
 
     def _backward_seed(self, loss: torch.Tensor):
         """d loss / d loss for a scalar loss, cached per (dtype, device); None otherwise."""
@@ -1054,11 +1093,14 @@ class _FlatTorchOptimizer:
     format (checkpoints, continued use of the optimizer).  ``refresh`` re-reads the
     param group, so hyperparameter edits between steps (manual LR decay) apply."""
 
-    def __init__(self, opt, params, flat_p, flat_g, cfg):
+    def __init__(self, opt, params, flat_p, flat_g, cfg, clip: dict | None = None):
         from ..ops.optim import FlatOptimizer
 
         self.opt = opt
         self.params = params
+        # the Trainer's gradient clipping: OptimConfig fields kept over every refresh
+        self.clip = dict(clip or {})
+        cfg = dataclasses.replace(cfg, **self.clip)
         self.cfg = cfg
         self.flat = FlatOptimizer(flat_p, flat_g, cfg)
         self._key = _group_key(opt)
@@ -1097,6 +1139,7 @@ class _FlatTorchOptimizer:
         cfg = _optim_config(self.opt)
         if cfg is None or cfg.name != self.cfg.name:
             return None
+        cfg = dataclasses.replace(cfg, **self.clip)
         if cfg == self.cfg:
             return False
         self.cfg = self.flat.cfg = cfg
@@ -1125,7 +1168,7 @@ class _FlatTorchOptimizer:
             o += n
 
 
-def _flat_optimizer_for(opt, ddp):
+def _flat_optimizer_for(opt, ddp, clip: dict | None = None):
     """_FlatTorchOptimizer for ``opt`` if it is a plain Adam/SGD whose one param group
     is a contiguous span of the flat buffers on a GPU, else None (torch's step runs)."""
     from ..ops.mlp import _flat_view_of
@@ -1142,4 +1185,4 @@ def _flat_optimizer_for(opt, ddp):
     flat_g = _flat_view_of([p.grad for p in params])
     if flat_p is None or flat_g is None:
         return None
-    return _FlatTorchOptimizer(opt, params, flat_p, flat_g, cfg)
+    return _FlatTorchOptimizer(opt, params, flat_p, flat_g, cfg, clip)
