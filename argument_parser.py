@@ -36,6 +36,12 @@ def build_parser(description: str | None = None) -> argparse.ArgumentParser:
                            "(torch.nn.utils.clip_grad_norm_ per optimizer; the module engine's flat kernel does it)")
     clip.add_argument("--clip_grad_value", type=float, default=0.0,
                       help="> 0: clamp every gradient element to [-F, F] before the optimizer step")
+    p.add_argument("--eval_every", type=int, default=0,
+                   help="> 0: evaluate both models on a held-out set after every K-th iteration and after the "
+                        "last one (val/lossX, val/lossY; val/accX, val/accY with --loss ce); 0 = off")
+    p.add_argument("--val_samples", type=int, default=512,
+                   help="size of the held-out set (a new draw of the training distribution, seed + 1, the same "
+                        "on every rank); used only with --eval_every")
     p.add_argument("--loss", choices=["mse", "ce"], default="mse")
     p.add_argument("--n_samples", type=int, default=512, help="ToyData size (toy_model_and_data.py:29)")
     p.add_argument("--per_rank_data", action="store_true",

@@ -111,6 +111,10 @@ def main(argv=None):
         # a model's norm would span the stages on several GPUs: not built here
         raise SystemExit("demo_one_model_multi_gpu.py: --clip_grad_norm / --clip_grad_value are not supported with "
                          "a layer-split model (the gradient norm would span the stages' GPUs); use demo.py")
+    if config.eval_every > 0:
+        # the evaluation kernel takes whole models; a split model's forward spans the stages' GPUs
+        raise SystemExit("demo_one_model_multi_gpu.py: --eval_every is not supported with a layer-split model "
+                         "(held-out evaluation runs whole models on one GPU); use demo.py")
     if config.dry_run:
         os.environ["WANDB_MODE"] = "dryrun"
     K = config.gpus_per_proc

@@ -47,11 +47,20 @@ class LitToyModel(LightningModule):
         self.log("loss/lossY", loss_y)
         return loss
 
+    def validation_step(self, batch, batch_idx):
+        x, y = batch
+        out_x, out_y = self(x)
+        loss_x, loss_y, _ = self.loss.pair(out_x, out_y, y)
+        self.log("val_loss_X", loss_x)
+        self.log("val_loss_Y", loss_y)
+
     def fused_spec(self):
         """What training_step computes, for the in-repo Trainer's fused train-step engine:
         optimizer i trains models[i] on MSE(models[i](x), y) of the same batch (the
-        returned loss_X + loss_Y over two independent models), logged as metrics[i]."""
-        return {"models": [self.model_X, self.model_Y], "loss": "mse", "metrics": ["loss/lossX", "loss/lossY"]}
+        returned loss_X + loss_Y over two independent models), logged as metrics[i];
+        validation_step logs MSE(models[i](x), y) as val_metrics[i]."""
+        return {"models": [self.model_X, self.model_Y], "loss": "mse", "metrics": ["loss/lossX", "loss/lossY"],
+                "val_metrics": ["val_loss_X", "val_loss_Y"]}
 
     def configure_optimizers(self):
         return [torch.optim.Adam(self.model_X.parameters(), lr=self.lr),
@@ -83,6 +92,10 @@ def get_args(argv=None):
                    help="resume: a checkpoint file, or 'last' for the newest one under <root_dir>/lightning_logs")
     p.add_argument("--every_n_train_steps", type=int, default=0,
                    help="also save lightning_logs/version_N/checkpoints/last.ckpt every N batches")
+    p.add_argument("--val_samples", type=int, default=0,
+                   help="> 0: validate on a held-out set of this size (ToyData.held_out, seed + 1); 0 = off")
+    p.add_argument("--check_val_every_n_epoch", type=int, default=1,
+                   help="with --val_samples: a validation epoch after every N-th training epoch")
     clip = p.add_mutually_exclusive_group()
     clip.add_argument("--clip_grad_norm", type=float, default=0.0,
                       help="Trainer(gradient_clip_val=F, gradient_clip_algorithm='norm'): per optimizer, before its step")
@@ -116,10 +129,18 @@ def main(argv=None):
     if a.clip_grad_norm > 0 or a.clip_grad_value > 0:  # Lightning's own Trainer takes the same two arguments
         extra.update(gradient_clip_val=a.clip_grad_norm or a.clip_grad_value,
                      gradient_clip_algorithm="norm" if a.clip_grad_norm > 0 else "value")
+    val_dl = None
+    if a.val_samples > 0:
+        val_dl = DataLoader(ds.held_out(a.val_samples, a.seed + 1), batch_size=a.batch_size,
+                            pin_memory=torch.cuda.is_available(), num_workers=a.num_workers)
+        extra["check_val_every_n_epoch"] = a.check_val_every_n_epoch
     trainer = TrainerCls(gpus=a.gpus, num_nodes=a.nnodes, max_steps=a.steps, precision=precision, accelerator=accel,
                          log_every_n_steps=min(50, len(dl) / a.batch_size), strategy="ddp",
                          default_root_dir=a.root_dir, enable_progress_bar=not a.no_progress, **extra)
-    trainer.fit(model, dl, ckpt_path=a.ckpt_path)
+    if val_dl is not None:
+        trainer.fit(model, dl, ckpt_path=a.ckpt_path, val_dataloaders=val_dl)
+    else:
+        trainer.fit(model, dl, ckpt_path=a.ckpt_path)
     if getattr(trainer, "global_rank", 0) == 0:
         sps = None
         if getattr(trainer, "fit_time", None):

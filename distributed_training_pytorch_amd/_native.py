@@ -225,6 +225,23 @@ class GemmArgs(ctypes.Structure):
     ]
 
 
+class EvalArgs(ctypes.Structure):
+    _fields_ = [
+        ("X", c_void_p),
+        ("Y", c_void_p),
+        ("params", c_void_p),
+        ("out", c_void_p),
+        ("ws", c_void_p),
+        ("row0", c_longlong),
+        ("row_stride", c_longlong),
+        ("n", c_longlong),
+        ("n_models", c_int),
+        ("loss", c_int),
+        ("bf16", c_int),
+        ("slope", c_float),
+    ]
+
+
 DT_F32, DT_BF16 = 0, 1
 MODE_GRAD, MODE_ADAM, MODE_SGD, MODE_XGMI_ADAM, MODE_XGMI_SGD = 0, 1, 2, 3, 4
 LOSS_MSE, LOSS_CE = 0, 1
@@ -266,6 +283,9 @@ def _declare(lib):
         "dtp_grad_norm": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
         "dtp_grad_norm_ws_bytes": (c_longlong, [c_int]),
         "dtp_clip_grad_norm": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+        "dtp_mlp_eval": (c_int, [P(EvalArgs), c_int, c_int, c_int, c_int, c_void_p]),
+        "dtp_mlp_eval_ws_bytes": (c_longlong, [c_longlong, c_int]),
+        "dtp_mlp_eval_one_launch_rows": (c_longlong, []),
         "dtp_mlp_stage_bwd_opt": (c_int, [P(StageMulti), P(OptArgs), c_int, c_int, c_int, c_int, c_int, c_void_p]),
         "dtp_mse_max_elems": (c_longlong, []),
         "dtp_mse_fwd": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p]),

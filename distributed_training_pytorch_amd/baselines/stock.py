@@ -89,6 +89,11 @@ class StockLoop:
         self.last = (float(rx) / (b * self.world), float(ry) / (b * self.world))
         self.samples += b
 
+    def forward_eval(self, x):
+        """Both models' outputs on x (the bare modules: no DDP bookkeeping for a forward
+        that is never followed by a backward)."""
+        return [getattr(m, "module", m)(x) for m in (self.mx, self.my)]
+
     def train(self, n: int):
         for _ in range(n):
             self.step()

@@ -105,6 +105,25 @@ struct DtpStageMulti {
 int dtp_mlp_stage_fwd_multi(const DtpStageMulti* m, int in, int h, int nl, int out, int final_act, void* stream);
 int dtp_mlp_stage_bwd(const DtpStageArgs* a, int in, int h, int nl, int out, int final_act, void* stream);
 
+// ---- held-out evaluation (eval.hip): forward + loss + reduction, all models in one launch ----
+struct DtpEvalArgs {
+  const float* X;        // [rows][IN]
+  const float* Y;        // [rows][OUT] (MSE) or [rows] class ids as float (CE), as DtpTrainArgs
+  const float* params;   // [n_models][P], torch order (the engines' flat rows)
+  double* out;           // [n_models][2] = {sum of per-sample losses, correct (CE; 0 for MSE)}
+  double* ws;            // dtp_mlp_eval_ws_bytes(n, n_models) bytes of scratch, may be null when that is 0
+  long long row0, row_stride, n;  // sample k reads row row0 + k * row_stride  (a rank's shard: rank, world)
+  int n_models;
+  int loss;              // DtpLoss
+  int bf16;              // bf16 compute instance (Stage<..., BF>), fp32 loss
+  float slope;
+};
+// out is a pure function of the arguments (fixed reduction order, no atomics): bitwise equal
+// run to run and under graph replay.  n == 0 writes zeros.
+int dtp_mlp_eval(const DtpEvalArgs* a, int in, int h, int nl, int out, void* stream);
+long long dtp_mlp_eval_ws_bytes(long long n, int n_models);
+long long dtp_mlp_eval_one_launch_rows(void);  // n up to here: one launch, no workspace
+
 // ---- persistent layer-split pipeline stage (split_train.hip) ----
 // One stage of a model split by layers over several GPUs, resident for n_steps
 // iterations: the stage's activation goes to the next stage and the input gradient

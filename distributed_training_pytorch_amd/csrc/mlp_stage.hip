@@ -7,6 +7,7 @@
 
 #include "dtp_api.h"
 #include "mlp_core.h"
+#include "mlp_shapes.h"
 #include "optim_core.h"
 
 namespace dtp {
@@ -185,33 +186,6 @@ __global__ __launch_bounds__(kBlock) void mlp_stage_bwd_opt_kernel(DtpStageMulti
 namespace {
 using dtp::check_launch;
 using dtp::set_err;
-
-// (IN, H, NL, OUT, FINAL_ACT): every contiguous layer range of the toy model
-// (layer-split stages) plus the train shapes as whole-model stages
-#define DTP_STAGE_SHAPES(X) \
-  X(2, 10, 5, 1, false)     \
-  X(2, 10, 4, 10, true)     \
-  X(10, 10, 4, 1, false)    \
-  X(2, 10, 3, 10, true)     \
-  X(10, 10, 3, 10, true)    \
-  X(10, 10, 3, 1, false)    \
-  X(2, 10, 2, 10, true)     \
-  X(10, 10, 2, 10, true)    \
-  X(10, 10, 2, 1, false)    \
-  X(2, 10, 1, 10, true)     \
-  X(10, 10, 1, 10, true)    \
-  X(10, 10, 1, 1, false)    \
-  X(2, 10, 3, 1, false)     \
-  X(2, 10, 5, 2, false)     \
-  X(2, 10, 5, 4, false)     \
-  X(2, 15, 5, 1, false)     \
-  X(2, 15, 5, 4, false)     \
-  X(4, 15, 5, 4, false)
-
-// whole-model shapes that also have bf16-compute instances (autocast / precision='bf16')
-#define DTP_STAGE_BF16_SHAPES(X) \
-  X(2, 10, 5, 1, false)          \
-  X(2, 10, 5, 4, false)
 
 template <class S>
 int launch_stage_fwd(const DtpStageArgs* a, hipStream_t st) {

@@ -29,11 +29,25 @@ class ToyData(Dataset):
         self.X = v.unsqueeze(1).repeat(1, in_features).contiguous()
         ys = [torch.randn(1, generator=g) * 0.5 + v[i] ** 2 for i in range(n)]
         self.Y = torch.stack(ys).reshape(n, 1).contiguous()
+        self.edges = None
         if classes:
             # classification variant for the cross-entropy option: bucket y into classes
             edges = torch.quantile(self.Y.view(-1), torch.linspace(0, 1, classes + 1)[1:-1])
             self.Y = torch.bucketize(self.Y.view(-1), edges).float().view(n, 1)
+            self.edges = edges
         self.classes = classes
+        self.in_features = in_features
+
+    def held_out(self, n: int, seed: int) -> "ToyData":
+        """A new draw of the same distribution for validation.  With ``classes`` its labels
+        are bucketed by THIS set's edges: a held-out set bucketed by its own quantiles would
+        carry different labels for the same y."""
+        h = ToyData(n, seed=seed, in_features=self.in_features, classes=0)
+        if self.classes:
+            h.Y = torch.bucketize(h.Y.view(-1), self.edges).float().view(n, 1)
+            h.edges = self.edges
+            h.classes = self.classes
+        return h
 
     def __getitem__(self, idx):
         return self.X[idx], self.Y[idx]

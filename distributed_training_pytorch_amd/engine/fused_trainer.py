@@ -20,6 +20,7 @@ its global mean loss into a device ring (``loss_log``) read lazily.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -568,6 +569,40 @@ class FusedTrainer:
         P, n = self.spec.P, self.n_models
         buf = self.comm_buf.clone()
         return buf[:n * P].view(n, P), buf[n * P:n * P + n]
+
+    @torch.no_grad()
+    def evaluate(self, X: torch.Tensor | None = None, Y: torch.Tensor | None = None) -> dict:
+        """Mean loss (and, for cross-entropy, accuracy) of every model on (X, Y) -- default:
+        the training set -- with the weights after the last queued step.
+
+        One launch of the evaluation kernel (``ops/eval.py``) on the engine's stream, behind
+        everything queued; rank r takes rows ``r::world`` (no padding, no sample counted
+        twice), then ONE all-reduce of the [n_models, 2] fp64 sums and the count.  Every rank
+        returns the same ``{"loss": float32 [n_models], "accuracy": float32 [n_models] or
+        None, "count": int}``.  Reads the weights only: parameters, moments, step counters,
+        the loss ring, the sampler ring and the exchange epochs are untouched.  Syncs (the
+        result goes to the host)."""
+        from ..ops.eval import EvalResult, evaluate as eval_sums, shard_rows
+
+        if (X is None) != (Y is None):
+            raise ValueError("evaluate: pass both X and Y, or neither")
+        X = self.X if X is None else X.to(self.device).contiguous().float()
+        Y = self.Y if Y is None else Y.to(self.device).contiguous().float()
+        nm = self.n_models
+        n = shard_rows(X.shape[0], self.rank, self.world)
+        buf = getattr(self, "_eval_buf", None)
+        if buf is None:
+            buf = self._eval_buf = torch.zeros(2 * nm + 1, dtype=torch.float64, device=self.device)
+        ctx = torch.cuda.device(self.device) if self.device.type == "cuda" else contextlib.nullcontext()
+        with ctx:
+            eval_sums(self.params, self.spec, X, Y, loss=self.cfg.loss, bf16=self.cfg.precision == "bf16",
+                      row0=self.rank, row_stride=self.world, n=n, out=buf[:2 * nm].view(nm, 2))
+            buf[2 * nm:].fill_(float(n))
+            if self.world > 1:
+                comm_util.all_reduce_(buf, self.group)
+            host = buf.cpu()
+        res = EvalResult(host[:2 * nm].view(nm, 2), int(host[2 * nm].item()), self.spec.out_features, self.cfg.loss)
+        return {"loss": res.mean_loss, "accuracy": res.accuracy, "count": res.count}
 
     def exchange_stats_reset(self) -> None:
         """Zero the in-kernel exchange's wait / publish counters (status words [4..14),

@@ -117,6 +117,76 @@ def _clip_value(config) -> float:
     return max(float(getattr(config, "clip_grad_value", 0.0) or 0.0), 0.0)
 
 
+class _Validation:
+    """``--eval_every K``: the held-out set, when it is due, and rank 0's ``val/*`` rows.
+
+    The set is ``train.held_out(--val_samples, seed + 1)`` of the SHARED training set (the
+    same rows and, with ``--loss ce``, the same label edges on every rank even with
+    ``--per_rank_data``); rank r evaluates rows ``r::world`` of it."""
+
+    def __init__(self, config, train_ds, rank, world, device, logger):
+        self.every = max(int(getattr(config, "eval_every", 0) or 0), 0)
+        self.iters, self.rank, self.world, self.logger = config.iters, rank, world, logger
+        self.ce = config.loss == "ce"
+        self.last: dict | None = None
+        self.X = self.Y = None
+        if self.every:
+            if config.per_rank_data:
+                train_ds = ToyData(n=config.n_samples, seed=config.seed, classes=train_ds.classes)
+            held = train_ds.held_out(int(config.val_samples), config.seed + 1)
+            self.X, self.Y = held.device_tensors(device)
+
+    def due(self, done: int) -> bool:
+        """After ``done`` iterations: every K-th, and the last one."""
+        return bool(self.every) and done > 0 and (done % self.every == 0 or done == self.iters)
+
+    def to_next(self, done: int) -> int:
+        """Iterations from ``done`` to the next evaluation point (launch chunks are cut there)."""
+        return self.every - done % self.every if self.every else 1 << 62
+
+    def sums_torch(self, forward) -> tuple[torch.Tensor, int]:
+        """This rank's shard through ``forward(x) -> outputs per model`` and torch's loss: the
+        sums of ``ops.eval.evaluate`` (fp32 per-sample values added in fp64)."""
+        x, y = self.X[self.rank::self.world].contiguous(), self.Y[self.rank::self.world].contiguous()
+        n = x.shape[0]
+        with torch.no_grad():
+            outs = forward(x) if n else []
+            sums = torch.zeros(2, 2, dtype=torch.float64, device=self.X.device)
+            for i, o in enumerate(outs):
+                o = o.float()
+                if self.ce:
+                    cls = y.view(-1).long()
+                    sums[i, 0] = torch.nn.functional.cross_entropy(o, cls, reduction="none").double().sum()
+                    sums[i, 1] = (o.argmax(1) == cls).sum().double()
+                else:
+                    sums[i, 0] = ((o - y.view_as(o)) ** 2).sum(1).double().sum()
+        return sums, n
+
+    def reduce(self, sums: torch.Tensor, n: int, out_features: int) -> dict:
+        """One all-reduce of the sums and the count -> the dict of ``FusedTrainer.evaluate``."""
+        from ..ops.eval import EvalResult
+
+        buf = torch.cat([sums.reshape(-1), torch.tensor([float(n)], dtype=torch.float64, device=sums.device)])
+        host = comm_util.all_reduce_(buf).cpu()
+        res = EvalResult(host[:-1].view(-1, 2), int(host[-1].item()), out_features, "ce" if self.ce else "mse")
+        return {"loss": res.mean_loss, "accuracy": res.accuracy, "count": res.count}
+
+    def report(self, done: int, res: dict) -> None:
+        self.last = res
+        row = {"val/lossX": float(res["loss"][0]), "val/lossY": float(res["loss"][1])}
+        if res["accuracy"] is not None:
+            row.update({"val/accX": float(res["accuracy"][0]), "val/accY": float(res["accuracy"][1])})
+        self.logger.log(row, step=done)
+
+    def summary(self) -> dict:
+        if self.last is None:
+            return {}
+        out = {"val_loss": [float(v) for v in self.last["loss"]]}
+        if self.last["accuracy"] is not None:
+            out["val_acc"] = [float(v) for v in self.last["accuracy"]]
+        return out
+
+
 def _progress(rank, total, config):
     if rank != 0 or config.no_progress:
         return None
@@ -192,6 +262,7 @@ def _train_fused(config, device, rank, world, logger, faults) -> dict:
     it = start
     chunk = max(1, min(config.log_every, config.steps_per_launch))
     timer = PhaseTimer(device)
+    val = _Validation(config, ds, rank, world, device, logger)
 
     def ckpt_due(i):
         return bool(config.checkpoint_dir and config.checkpoint_every and i % config.checkpoint_every == 0)
@@ -214,6 +285,8 @@ def _train_fused(config, device, rank, world, logger, faults) -> dict:
         n = min(chunk, config.iters - it)
         if faults.armed() and it <= config.fail_at_iter < it + n:
             n = config.fail_at_iter - it
+        n = min(n, val.to_next(it))  # launches are cut at the evaluation points
+        val_due = n > 0 and val.due(it + n)
         if n > 0:
             with timer.phase("train_chunk"):
                 tr.train(n)
@@ -222,10 +295,15 @@ def _train_fused(config, device, rank, world, logger, faults) -> dict:
                 process(pending)
             pending = (it, n, handle)
             it += n
-        if pending is not None and (it >= config.iters or ckpt_due(it) or
+        if pending is not None and (it >= config.iters or ckpt_due(it) or val_due or
                                     (faults.armed() and it >= config.fail_at_iter)):
             process(pending)
             pending = None
+        if val_due:
+            # stream-ordered behind the chunk just queued; its loss rows are logged (above)
+            # before the val/* row of step `it`
+            with timer.phase("validation"):
+                val.report(it, tr.evaluate(val.X, val.Y))
         faults.check(it)
         if ckpt_due(it):
             tr.synchronize()
@@ -249,6 +327,7 @@ def _train_fused(config, device, rank, world, logger, faults) -> dict:
     samples = geom.batch * (it - start) * world
     tr.close()
     return {"final_loss": final, "iters": it, "samples_per_s": samples / max(dt, 1e-9), "engine": "fused",
+            **val.summary(),
             **({"phases": timer.summary()} if trace_enabled() else {})}
 
 
@@ -295,6 +374,22 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
     if pbar is not None and start:
         pbar.update(start)
     timer = PhaseTimer(device)
+    val = _Validation(config, ds, rank, world, device, logger)
+    val_native = device.type == "cuda" and bank.spec.native_supported(bf16=_compute_dtype(config) == torch.bfloat16)
+
+    def _validate(done):
+        # between graph replays, never inside one: the toy shapes in one launch of the
+        # evaluation kernel over the bank's flat rows, wide models through the bank's forward
+        if val_native:
+            from ..ops.eval import evaluate as eval_sums, shard_rows
+
+            n = shard_rows(val.X.shape[0], rank, world)
+            sums = eval_sums(bank.flat.detach(), bank.spec, val.X, val.Y, loss=config.loss,
+                             bf16=_compute_dtype(config) == torch.bfloat16, row0=rank, row_stride=world, n=n)
+        else:
+            sums, n = val.sums_torch(bank)
+        val.report(done, val.reduce(sums, n, out_f))
+
     t0 = time.perf_counter()
     # per-step losses stay on the device; the global means are reduced and logged once
     # per log_every steps (one all-reduce of the chunk, one host sync), with the same
@@ -423,6 +518,10 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
                 _flush(wait=sync_flush)  # no device sync: the rows are logged when they arrive
         if pbar is not None:
             pbar.update(1)
+        if val.due(it + 1):
+            _flush()  # the loss rows up to here first: the log stays in step order
+            with timer.phase("validation"):
+                _validate(it + 1)
         if config.checkpoint_dir and config.checkpoint_every and (it + 1) % config.checkpoint_every == 0:
             _flush()
             _save(it + 1)
@@ -446,7 +545,7 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
         _save(config.iters)
     return {"final_loss": last, "iters": config.iters,
             "samples_per_s": geom.batch * (config.iters - start) * world / max(dt, 1e-9),
-            "steady_samples_per_s": steady, "engine": "module",
+            "steady_samples_per_s": steady, "engine": "module", **val.summary(),
             "graph_replays": stepper.replays,
             # clipping by norm: each model's gradient norm at the last step, before clipping
             **({"grad_norm": opt.grad_norm.tolist()} if _clip_norm(config) > 0 else {}),
@@ -476,6 +575,8 @@ def _train_stock(config, device, rank, world, logger, faults) -> dict:
                      clip_grad_norm=_clip_norm(config), clip_grad_value=_clip_value(config))
     pbar = _progress(rank, config.iters, config)
     timer = PhaseTimer(device)
+    val = _Validation(config, ds, rank, world, device, logger)
+    val.ce = False  # the stock loop trains one-output models with MSE whatever --loss says
     t0 = time.perf_counter()
     for it in range(config.iters):
         faults.check(it)
@@ -484,14 +585,23 @@ def _train_stock(config, device, rank, world, logger, faults) -> dict:
         if rank == 0:
             logger.log({"loss/lossX": loop.last[0]}, step=it, commit=False)
             logger.log({"loss/lossY": loop.last[1]}, step=it)
+        if val.due(it + 1):
+            with timer.phase("validation"):
+                val.report(it + 1, val.reduce(*val.sums_torch(loop.forward_eval), 1))
         if pbar is not None:
             pbar.update(1)
     dt = time.perf_counter() - t0
     if pbar is not None:
         pbar.close()
+    if config.checkpoint_dir:
+        # the trained weights as the other engines' flat rows (torch order), so a run's
+        # validation loss can be checked against them; the stock loop does not resume
+        flat = torch.stack([torch.nn.utils.parameters_to_vector(m.parameters()).detach() for m in (loop.mx, loop.my)])
+        checkpoint.save({"engine": "stock", "params": flat, "config": vars(config)}, config.checkpoint_dir,
+                        config.iters)
     loop.close()
     return {"final_loss": list(loop.last), "iters": config.iters,
-            "samples_per_s": loop.samples * world / max(dt, 1e-9), "engine": "stock",
+            "samples_per_s": loop.samples * world / max(dt, 1e-9), "engine": "stock", **val.summary(),
             **({"phases": timer.summary()} if trace_enabled() else {})}
 
 

@@ -17,6 +17,8 @@ class LightningModule(nn.Module):
         super().__init__()
         self.trainer = None
         self._logged: dict[str, float] = {}
+        # inside a validation loop: self.log writes here (the replayed train graphs own _logged)
+        self._val_logged: dict | None = None
 
     # ---- user hooks -----------------------------------------------------------
     def training_step(self, batch, batch_idx, optimizer_idx=0):  # pragma: no cover - abstract
@@ -31,9 +33,23 @@ class LightningModule(nn.Module):
     def on_train_end(self):
         pass
 
+    def validation_step(self, batch, batch_idx):
+        """Optional (PL 1.5): override it and log through ``self.log``; the Trainer reduces
+        every logged value to the epoch mean weighted by batch size.  A module that does not
+        override it is never validated."""
+
+    def on_validation_epoch_start(self):
+        pass
+
+    def on_validation_epoch_end(self):
+        pass
+
     # ---- services ---------------------------------------------------------------
     def log(self, name: str, value, prog_bar: bool = False, sync_dist: bool = False, **_):
         v = value.detach() if isinstance(value, torch.Tensor) else torch.tensor(float(value))
+        if getattr(self, "_val_logged", None) is not None:
+            self._val_logged[name] = v
+            return
         self._logged[name] = v
 
     @property

@@ -57,11 +57,35 @@ class CSVLogger:
         self.dir.mkdir(parents=True)
         self._f = open(self.dir / "metrics.csv", "w", newline="")
         self._w = None
+        self._widen = False
+
+    def allow_new_columns(self) -> None:
+        """From now on a row with metrics the header lacks widens the header (validation
+        metrics arrive after the first training rows) instead of dropping them."""
+        self._widen = True
+
+    def _fit_header(self, keys) -> None:
+        """Add the columns of ``keys`` the header lacks: the file is rewritten once under
+        the wider header, the rows written so far keep their text, their new cells empty."""
+        if not self._widen or self._w is None:
+            return
+        new = [k for k in keys if k not in self._w.fieldnames]
+        if not new:
+            return
+        path = self.dir / "metrics.csv"
+        self._f.close()
+        with open(path, newline="") as f:
+            old = list(csv.DictReader(f))
+        self._f = open(path, "w", newline="")
+        self._w = csv.DictWriter(self._f, fieldnames=[*self._w.fieldnames, *new], extrasaction="ignore")
+        self._w.writeheader()
+        self._w.writerows(old)
 
     def log(self, step: int, metrics: dict):
         if self.dir is None:
             return
         row = {"step": step, **{k: float(v) for k, v in metrics.items()}}
+        self._fit_header(row.keys())
         if self._w is None:
             self._w = csv.DictWriter(self._f, fieldnames=list(row.keys()), extrasaction="ignore")
             self._w.writeheader()
@@ -75,6 +99,7 @@ class CSVLogger:
         if self._w is None:
             self.log(steps[0], {**dict(zip(names, rows[0])), "train_loss": sum(rows[0])})
             steps, rows = steps[1:], rows[1:]
+        self._fit_header(["step", *names, "train_loss"])
         if list(self._w.fieldnames) == ["step", *names, "train_loss"]:
             # the csv module's own text for these rows (floats as repr, excel's \r\n), formatted
             # directly: ~5 us per row through DictWriter made the host, not the GPU, the
@@ -97,6 +122,7 @@ class CSVLogger:
         if self._w is None:
             self._w = csv.DictWriter(self._f, fieldnames=["step", *names, "train_loss"], extrasaction="ignore")
             self._w.writeheader()
+        self._fit_header(["step", *names, "train_loss"])
         r = rows.detach()
         if (nat.native_enabled() and os.environ.get("DTP_NATIVE_LOG", "1") != "0"
                 and r.device.type == "cpu" and r.dtype == torch.float32 and r.dim() == 2
@@ -302,7 +328,7 @@ class _MetricRing:
             for step, vals in zip(steps, rows):
                 self.logger.log(step, dict(zip(keys, vals)))
             self.logger.flush()
-            self.tr.callback_metrics = dict(zip(keys, rows[-1]))
+            self.tr.callback_metrics = {**dict(zip(keys, rows[-1])), **self.tr._val_metrics}
 
 
 class Trainer:
@@ -312,7 +338,8 @@ class Trainer:
                  enable_checkpointing: bool = True, enable_progress_bar: bool = True, seed: int | None = None,
                  use_graphs: bool = True, native_optimizers: bool = True, every_n_train_steps: int = 0,
                  engine: str = "auto", graph_copies: int | None = None, gradient_clip_val: float | None = None,
-                 gradient_clip_algorithm: str = "norm", **unused):
+                 gradient_clip_algorithm: str = "norm", check_val_every_n_epoch: int = 1,
+                 val_check_interval: int | None = None, **unused):
         if precision in (32, "32", "32-true"):
             self.autocast_dtype = None
         elif precision in ("bf16", "bf16-mixed"):
@@ -370,6 +397,14 @@ class Trainer:
         self.engine = engine
         self.engine_used = "module"
         self.fused_refused: str | None = None  # why fused_spec() was not trusted (checked on the first batch)
+        # validation (PL 1.5 subset): after every check_val_every_n_epoch-th epoch, or --
+        # val_check_interval, an int -- after every that many batches of those epochs
+        self.check_val_every_n_epoch = max(1, int(check_val_every_n_epoch or 1))
+        if val_check_interval is not None and (isinstance(val_check_interval, float) or int(val_check_interval) < 1):
+            raise ValueError(f"val_check_interval={val_check_interval!r}: an int count of batches >= 1")
+        self.val_check_interval = None if val_check_interval is None else int(val_check_interval)
+        self.val_fused_refused: str | None = None  # why fused_spec()'s val_metrics were not trusted
+        self._val_metrics: dict = {}
         self._skip_batches = 0
         self._batch_in_epoch = 0
         self._log_dir = None
@@ -408,8 +443,10 @@ class Trainer:
         return dl
 
     # ------------------------------------------------------------------ fit
-    def fit(self, model, train_dataloaders=None, train_dataloader=None, ckpt_path: str | None = None):
-        """Train ``model``.  ``ckpt_path`` resumes (PL's ``fit(ckpt_path=...)``): a
+    def fit(self, model, train_dataloaders=None, train_dataloader=None, ckpt_path: str | None = None, *,
+            val_dataloaders=None):
+        """Train ``model``.  ``val_dataloaders`` (keyword only) with a ``validation_step``:
+        validation epochs between training batches (``_run_validation``).  ``ckpt_path`` resumes (PL's ``fit(ckpt_path=...)``): a
         checkpoint file, or ``"last"`` for the newest ``last.ckpt`` / final checkpoint
         under ``{root}/lightning_logs``; weights, optimizer states, ``global_step``,
         epoch and the position inside the epoch are restored, so a restarted job
@@ -426,9 +463,11 @@ class Trainer:
         resume = self._resolve_ckpt(ckpt_path)
         if resume is not None:
             self._restore(model, opts, resume)
+        self._val_metrics = {}
+        val_dl = val_dataloaders if _has_validation_step(model) else None
         plan = self._fused_plan(model, opts, dl)
         if plan is not None:
-            done = self._fit_fused(model, opts, plan)
+            done = self._fit_fused(model, opts, plan, val_dl)
             if done is not None:
                 return done
         # the flat gradient buffer of FlatDDP also serves one process: fused kernels add
@@ -454,6 +493,11 @@ class Trainer:
         self._log_dir = logger.dir
         copies = self.graph_copies if stepper is not None else 1
         metrics = _MetricRing(self, logger, defer=copies)
+        vloader = None
+        if val_dl is not None:
+            vloader = self._val_loader(val_dl)
+            logger.allow_new_columns()
+        spe = len(loader) if hasattr(loader, "__len__") else None
         pbar = None
         if self.enable_progress_bar and self.global_rank == 0:
             try:
@@ -534,6 +578,9 @@ class Trainer:
                     if self.every_n_train_steps and self.global_step % self.every_n_train_steps == 0:
                         metrics.flush()
                         self._save(model, opts, "last.ckpt")
+                    if vloader is not None and self._val_due(self.current_epoch, batch_idx + 1, spe):
+                        metrics.flush()  # the training rows up to here first
+                        self._log_validation(logger, self._run_validation(model, vloader))
                     if 0 <= self.max_steps <= self.global_step:
                         done = True
                         break
@@ -629,9 +676,10 @@ class Trainer:
             return no("the dataset has no device_tensors()")
         prec = "fp32" if self.autocast_dtype is None else "bf16"
         return {"models": models, "names": names, "loss": loss, "optim": cfgs[0], "dataset": ds,
+                "val_names": list(fs.get("val_metrics") or []),
                 "batch": int(getattr(dl, "batch_size", None) or 1), "precision": prec, "spec": models[0].spec}
 
-    def _fit_fused(self, model, opts, plan):
+    def _fit_fused(self, model, opts, plan, val_dl=None):
         from ..engine.fused_trainer import EngineConfig, FusedTrainer
 
         models, names = plan["models"], plan["names"]
@@ -678,6 +726,44 @@ class Trainer:
         total = min(limits)
         logger = CSVLogger(self.root, self.global_rank)
         self._log_dir = logger.dir
+        vloader, vdev, vchecked = None, None, False
+        if val_dl is not None:
+            vloader = self._val_loader(val_dl)
+            logger.allow_new_columns()
+            vds = getattr(val_dl, "dataset", val_dl)
+            vnames = list(plan.get("val_names") or [])
+            if len(vnames) == len(models) and hasattr(vds, "device_tensors"):
+                vdev = vds.device_tensors(self.device)  # the engine's own evaluation kernel
+
+        def validate():
+            # weights back into the modules (stream-ordered copies) for the general loop;
+            # with declared val_metrics the engine evaluates them itself -- checked once
+            # against the general loop on the same weights, like fused_spec itself
+            nonlocal vdev, vchecked
+            if vdev is not None:
+                ev = tr.evaluate(*vdev)
+                res = {k: float(v) for k, v in zip(vnames, ev["loss"])}
+                if not vchecked:
+                    vchecked = True
+                    for i, m in enumerate(models):
+                        m.load_flat_(tr.model_params(i))
+                    ref = self._run_validation(model, vloader)
+                    tol = 1e-2 if plan["precision"] == "bf16" else 1e-5
+                    bad = [k for k in vnames if k not in ref or not math.isclose(
+                        res[k], ref[k], rel_tol=tol, abs_tol=1e-2 if tol > 1e-3 else 1e-6)]
+                    if bad or set(ref) != set(vnames):
+                        k = bad[0] if bad else sorted(set(ref) ^ set(vnames))[0]
+                        self.val_fused_refused = (f"{k} of validation_step is {ref.get(k)!r}, the declared "
+                                                  f"val_metrics give {res.get(k)!r}")
+                        if self.global_rank == 0:
+                            rank_print(0, f"Trainer: not using the engine's evaluation ({self.val_fused_refused})")
+                        vdev = None
+                        res = ref
+                return res
+            for i, m in enumerate(models):
+                m.load_flat_(tr.model_params(i))
+            return self._run_validation(model, vloader)
+
         model.on_train_start()
         if self.global_rank == 0:
             rank_print(0, f"Trainer: fused train-step engine ({tr.comm} comm, {plan['precision']})")
@@ -706,6 +792,9 @@ class Trainer:
                 n = min(tr.cfg.steps_per_launch if steady_t0 is not None else _STEADY_AFTER, total - self.global_step)
                 if self.every_n_train_steps:
                     n = min(n, self.every_n_train_steps - self.global_step % self.every_n_train_steps)
+                val_at = self._val_next(self.global_step, spe) if vloader is not None else None
+                if val_at is not None:  # launches are cut at the validation points
+                    n = min(n, val_at - self.global_step)
                 s0 = self.global_step
                 tr.train(n)
                 self.global_step += n
@@ -727,6 +816,11 @@ class Trainer:
                         pending = None
                     self._export_fused_state(tr, models, opts)
                     self._save(model, opts, "last.ckpt")
+                if self.global_step == val_at:
+                    if pending is not None:  # the training rows up to here first
+                        drain(pending)
+                        pending = None
+                    self._log_validation(logger, validate())
             if pending is not None:
                 drain(pending)
                 pending = None
@@ -737,7 +831,7 @@ class Trainer:
             if steady_t0 is not None and self.global_step > steady_from:
                 self.steady_time, self.steady_steps = t1 - steady_t0, self.global_step - steady_from
             if last is not None:
-                self.callback_metrics = {**dict(zip(names, last)), "train_loss": sum(last)}
+                self.callback_metrics = {**dict(zip(names, last)), "train_loss": sum(last), **self._val_metrics}
         finally:
             self._export_fused_state(tr, models, opts)
             tr.close()
@@ -838,6 +932,112 @@ class Trainer:
                 elif o.param_groups[0].get("momentum", 0.0):
                     o.state[p] = {"momentum_buffer": tr.m[i, off:off + n].view_as(p).clone()}
                 off += n
+
+    # ------------------------------------------------------------------ validation
+    def _val_due(self, epoch: int, batches_done: int, spe: int | None) -> bool:
+        """Is a validation epoch due after ``batches_done`` batches of ``epoch`` (of ``spe``)?"""
+        if (epoch + 1) % self.check_val_every_n_epoch:
+            return False
+        if self.val_check_interval is not None:
+            return batches_done % self.val_check_interval == 0
+        return spe is not None and batches_done == spe
+
+    def _val_next(self, step: int, spe: int) -> int | None:
+        """The first global step after ``step`` at which ``_val_due`` holds (epochs of ``spe``
+        batches), None if there is none."""
+        every = self.check_val_every_n_epoch
+        if self.val_check_interval is None:
+            return (step // (spe * every) + 1) * spe * every
+        vci = self.val_check_interval
+        if vci > spe:
+            return None
+        base = (-(-(step // spe + 1) // every) * every - 1) * spe  # first step of the next validated epoch
+        at = base + (max(step - base, 0) // vci + 1) * vci
+        return at if at <= base + spe else base + every * spe + vci
+
+    def _val_loader(self, dl):
+        """This rank's validation batches: rows ``rank::world`` of the set, unpadded (no
+        sample counted twice, unlike a DistributedSampler) -- device slices when the dataset
+        has ``device_tensors``, else a strided ``Subset`` behind a DataLoader."""
+        ds = getattr(dl, "dataset", dl)
+        bs = int(getattr(dl, "batch_size", None) or 1)
+        r, w = self.global_rank, self.world_size
+        if hasattr(ds, "device_tensors"):
+            X, Y = ds.device_tensors(self.device)
+            X, Y = X[r::w].contiguous(), Y[r::w].contiguous()
+            return [[X[i:i + bs], Y[i:i + bs]] for i in range(0, X.shape[0], bs)]
+        if w > 1:
+            from torch.utils.data import DataLoader, Subset
+
+            return DataLoader(Subset(ds, range(r, len(ds), w)), batch_size=bs,
+                              num_workers=getattr(dl, "num_workers", 0))
+        return dl
+
+    def _run_validation(self, model, vloader) -> dict:
+        """One validation epoch, eager, outside the captured train graphs: ``model.eval()``
+        and ``no_grad``; every value ``validation_step`` logs is reduced to the epoch mean
+        weighted by batch size, summed over ranks as (value x size, size).  Returns
+        {name: float}, the same on every rank."""
+        was_training = model.training
+        model.eval()
+        sums: dict = {}
+        try:
+            model.on_validation_epoch_start()
+            with torch.no_grad():
+                for bi, batch in enumerate(vloader):
+                    batch = [b.to(self.device, non_blocking=True) for b in batch]
+                    size = int(batch[0].shape[0])
+                    model._val_logged = {}
+                    with self._autocast():
+                        model.validation_step(batch, bi)
+                    for k, v in model._val_logged.items():
+                        s = sums.setdefault(k, [torch.zeros((), dtype=torch.float64, device=self.device), 0])
+                        s[0] += v.to(self.device).double().reshape(-1)[0] * size
+                        s[1] += size
+        finally:
+            model._val_logged = None
+            model.train(was_training)
+        keys = sorted(sums)
+        if self.world_size > 1:  # a rank whose shard is empty logged nothing: agree on the names
+            every = [None] * self.world_size
+            dist.all_gather_object(every, keys)
+            keys = sorted({k for ks in every for k in ks})
+        out = {}
+        if keys:
+            zero = torch.zeros((), dtype=torch.float64, device=self.device)
+            buf = torch.stack([sums[k][0] if k in sums else zero for k in keys] +
+                              [torch.tensor(float(sums[k][1] if k in sums else 0), dtype=torch.float64,
+                                            device=self.device) for k in keys])
+            host = comm_util.all_reduce_(buf).cpu().tolist()
+            n = len(keys)
+            out = {k: host[i] / host[n + i] for i, k in enumerate(keys) if host[n + i] > 0}
+        model.on_validation_epoch_end()
+        return out
+
+    def _log_validation(self, logger, res: dict) -> None:
+        self._val_metrics = dict(res)
+        self.callback_metrics = {**self.callback_metrics, **res}
+        if res:
+            logger.log(self.global_step, res)
+            logger.flush()
+
+    def validate(self, model, dataloaders=None, ckpt_path: str | None = None) -> list:
+        """One validation epoch of ``model`` over ``dataloaders`` (PL's ``Trainer.validate``):
+        a list with one dict of the reduced metrics, also merged into ``callback_metrics``.
+        ``ckpt_path``: weights from a checkpoint file (or ``"last"``) first."""
+        if not _has_validation_step(model):
+            raise RuntimeError("Trainer.validate: the LightningModule defines no validation_step")
+        if not hasattr(self, "device"):
+            self._setup()
+        model.trainer = self
+        model.to(self.device)
+        path = self._resolve_ckpt(ckpt_path)
+        if path is not None:
+            model.load_state_dict(torch.load(path, map_location="cpu", weights_only=True)["state_dict"])
+        res = self._run_validation(model, self._val_loader(dataloaders))
+        self._val_metrics = dict(res)
+        self.callback_metrics = {**self.callback_metrics, **res}
+        return [res]
 
     # ------------------------------------------------------------------ checkpoints
     def _ckpt_dir(self) -> Path | None:
@@ -1029,6 +1229,14 @@ class Trainer:
         if dist.is_initialized():
             comm_util.barrier()
             dist.destroy_process_group()
+
+
+def _has_validation_step(model) -> bool:
+    """Does the module define its own ``validation_step`` (the base class's does nothing)?"""
+    from .module import LightningModule
+
+    f = getattr(type(model), "validation_step", None)
+    return callable(f) and f is not LightningModule.validation_step
 
 
 class _StaticBatch:
