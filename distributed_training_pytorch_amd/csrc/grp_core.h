@@ -119,6 +119,27 @@ DTP_DEV uint32_t grp_hash3(uint32_t a, uint32_t b, uint32_t c) {
   return a ^ ((b << 11) | (b >> 21)) ^ ((c << 22) | (c >> 10)) ^ 0x9E3779B9u;
 }
 
+#ifndef DTP_GRP_ROWS
+// The split-batch members park their per-wave dW tiles in PAYLOAD order: one row per wave,
+// payload float f of the 3-float exchange (parameter f, the loss at P) at grp_row_pos(f).
+// 1: wave 0 forms its granules straight from the rows (one aligned 16-byte LDS read per wave
+//    and granule) right after the park barrier -- no staging pass through pub[], no staging
+//    barrier -- and every thread's own sums run behind the publish (grp_allreduce_split3_ng's
+//    RNW form);
+// 2: the row layout with the staged exchange (A/B: the layout alone);
+// 0: the tile layout and the staged exchange.
+#define DTP_GRP_ROWS 1
+#endif
+#ifndef DTP_GRP_GRC
+// 1: a split-batch step of 4 members (one rank, batch 256) runs an instance with the member
+// count as a template constant: poll items per lane and the sums' trip counts are constants,
+// the per-step dispatch between the poll-loop variants is gone
+#define DTP_GRP_GRC 1
+#endif
+// a payload-order row: granule q = floats [4q, 4q + 3), one pad float (aligned 16-byte reads)
+DTP_HD constexpr int grp_row_pos(int f) { return 4 * (f / 3) + f % 3; }
+DTP_HD constexpr int grp_row_floats(int P) { return 4 * grp_ng3(P); }
+
 struct GrpCtx {
   void* buf;    // [2][n_models][GR][slot16] granules
   int* status;  // sticky timeout word pair (nullable)
@@ -498,41 +519,85 @@ DTP_DEV float grp_allreduce_split(const GrpCtx& c, int model, float (&g)[NPT], f
 // gather and index request), run exactly once by every thread while its memory requests are
 // in flight: the publisher after its stores, a poller between its first poll's issue and
 // its consumption.
-template <int P, int NPT, int NTHREADS, int NG, class OverlapFn>
-DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT], float loss, unsigned epoch, int tid,
-                                      bool& dead, float* __restrict__ lds, unsigned xcc, bool& plain, GrpProf* prof,
-                                      OverlapFn ov) {
+// GRC > 0: the member count as a constant (DTP_GRP_GRC; the caller guarantees c.GR == GRC).
+// RNW > 0 (DTP_GRP_ROWS = 1): the member's per-wave partial sums are parked in RNW payload-order
+// rows (rows + w * RSTRIDE, grp_row_pos).  Wave 0 forms granule q from one float4 per row,
+// summed in wave order from 0.f -- the operations of the caller's own() sums, so it publishes
+// the bits the member adds for itself -- with no staging pass and no staging barrier; pub[]
+// is not used.  own() fills g and loss from the rows (LDS reads only, counted on lgkmcnt, not
+// on the polls' vmcnt): the pollers run it between their first poll's issue and its
+// consumption, wave 0 behind the publisher-first barrier.  Every read of the rows completes
+// before the final barrier, so the next step's park never races with them.
+template <int P, int NPT, int NTHREADS, int NG, int GRC = 0, int RNW = 0, int RSTRIDE = 0, class OverlapFn,
+          class OwnFn = std::nullptr_t>
+DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT], const float& loss, unsigned epoch,
+                                      int tid, bool& dead, float* __restrict__ lds, unsigned xcc, bool& plain,
+                                      GrpProf* prof, OverlapFn ov, const float* __restrict__ rows = nullptr,
+                                      OwnFn own = nullptr) {
   constexpr int NGF = grp_ng3(P), PS = grp_ps3(P);
+  constexpr bool kRows = RNW > 0;
+  static_assert(!kRows || (!std::is_same_v<OwnFn, std::nullptr_t> && RSTRIDE % 4 == 0 && RSTRIDE >= 4 * NG),
+                "the row form needs the caller's own sums and 16-byte aligned rows of NG granules");
+  static_assert(!kRows || !DTP_GRP_OVERLAP, "the row form runs the own sums, not ov(), inside the first poll");
+  const int GR = GRC > 0 ? GRC : c.GR;
   constexpr int NPOLL = NTHREADS - kWave;  // poller lanes (waves 1..)
   constexpr int slot = grp_slot16(P, NPT);
   static_assert(NGF <= slot, "a member's 3-float granules fit its slot of the exchange buffer");
   static_assert(NTHREADS > kWave, "one publisher wave and at least one poller wave");
   float* const pub = lds;
   float* const peer = lds + PS;  // peer[r * PS + i]: member r's float i
-  const size_t base = (size_t)((int)(epoch & 1u) * c.n_models + model) * c.GR;
+  const size_t base = (size_t)((int)(epoch & 1u) * c.n_models + model) * GR;
   // 1. the payload into LDS
+  if constexpr (!kRows) {
 #pragma unroll
-  for (int k = 0; k < NPT; ++k)
-    if (NPT * tid + k < P) pub[NPT * tid + k] = g[k];
-  if (tid == 0) {
-    pub[P] = loss;
-    pub[P + 1] = __uint_as_float(xcc);
+    for (int k = 0; k < NPT; ++k)
+      if (NPT * tid + k < P) pub[NPT * tid + k] = g[k];
+    if (tid == 0) {
+      pub[P] = loss;
+      pub[P + 1] = __uint_as_float(xcc);
 #pragma unroll
-    for (int i = P + 2; i < 3 * NGF; ++i) pub[i] = 0.f;
+      for (int i = P + 2; i < 3 * NGF; ++i) pub[i] = 0.f;
+    }
+    __syncthreads();
   }
-  __syncthreads();
   const __amdgpu_buffer_rsrc_t rs = xgmi_rsrc(c.buf);
   if (tid < kWave) {
     // 2a. wave 0 publishes every granule of this member (all its LDS reads first, then the
     // stores back to back)
     constexpr int MAXJ = (NG + kWave - 1) / kWave;
     float v[MAXJ][3];
+    if constexpr (kRows) {
+      float4 t[MAXJ][RNW];
 #pragma unroll
-    for (int j = 0; j < MAXJ; ++j) {
-      const int q = tid + j * kWave < NG ? tid + j * kWave : NG - 1;
-      v[j][0] = pub[3 * q];
-      v[j][1] = pub[3 * q + 1];
-      v[j][2] = pub[3 * q + 2];
+      for (int j = 0; j < MAXJ; ++j) {
+        const int q = tid + j * kWave < NG ? tid + j * kWave : NG - 1;
+#pragma unroll
+        for (int w = 0; w < RNW; ++w) t[j][w] = *reinterpret_cast<const float4*>(rows + w * RSTRIDE + 4 * q);
+      }
+#pragma unroll
+      for (int j = 0; j < MAXJ; ++j) {
+        const int q = tid + j * kWave < NG ? tid + j * kWave : NG - 1;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll
+        for (int w = 0; w < RNW; ++w) {
+          s0 += t[j][w].x;
+          s1 += t[j][w].y;
+          s2 += t[j][w].z;
+        }
+        // past the loss: the XCC id at float P + 1, then zeros (the rows hold nothing there)
+        const float xf = __uint_as_float(xcc);
+        v[j][0] = 3 * q == P + 1 ? xf : (3 * q > P + 1 ? 0.f : s0);
+        v[j][1] = 3 * q + 1 == P + 1 ? xf : (3 * q + 1 > P + 1 ? 0.f : s1);
+        v[j][2] = 3 * q + 2 == P + 1 ? xf : (3 * q + 2 > P + 1 ? 0.f : s2);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < MAXJ; ++j) {
+        const int q = tid + j * kWave < NG ? tid + j * kWave : NG - 1;
+        v[j][0] = pub[3 * q];
+        v[j][1] = pub[3 * q + 1];
+        v[j][2] = pub[3 * q + 2];
+      }
     }
 #pragma unroll
     for (int j = 0; j < MAXJ; ++j) {
@@ -550,12 +615,16 @@ DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT
       prof->rt_pub = __builtin_amdgcn_s_memrealtime();
     }
     if (DTP_GRP_OVERLAP) ov();
+    if constexpr (kRows && !DTP_GRP_PUB_FIRST) own();
   }
   if (DTP_GRP_PUB_FIRST) __syncthreads();
+  if constexpr (kRows && DTP_GRP_PUB_FIRST) {
+    if (tid < kWave) own();  // behind the barrier: the pollers do not wait for these sums
+  }
   if (tid >= kWave) {
     // 2b. item i = (peer index i / NG, granule i % NG), lane pl holds items pl + j NPOLL
     const int pl = tid - kWave;
-    const int total = (c.GR - 1) * NG;
+    const int total = (GR - 1) * NG;
     unsigned long long deadline = 0;
     unsigned spins = 0;
     if (prof) prof->t_pub = grp_clock();
@@ -619,7 +688,26 @@ DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT
       };
       u32x4 xa[PI], xb[PI];
       bool ovd = !DTP_GRP_OVERLAP;
-      if (!DTP_GRP_PIPE3) {  // one poll in flight (the default with 3-float granules)
+      if constexpr (kRows) {
+        // the first poll goes out, the own sums run while it is in flight (exactly once, also
+        // on a lane without items and in a dead launch); then one or two polls in flight
+        if (pending && !dead) issue(xa);
+        own();
+        if (!DTP_GRP_PIPE3) {
+          while (pending && !dead) {
+            consume(xa);
+            if (prof && spins == 0) prof->t_first = grp_clock();
+            if (!pending) break;
+            if (expired()) {
+              dead = true;
+              break;
+            }
+            issue(xa);
+          }
+          if (DTP_GRP_ZERO_MISSING && pending) zero_missing();
+          return;
+        }
+      } else if (!DTP_GRP_PIPE3) {  // one poll in flight (the default with 3-float granules)
         while (pending && !dead) {
           issue(xa);
           if (!ovd) {
@@ -634,7 +722,7 @@ DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT
         if (DTP_GRP_ZERO_MISSING && pending) zero_missing();
         return;
       }
-      if (pending && !dead) issue(xa);
+      if (!kRows && pending && !dead) issue(xa);
       if (!ovd) {
         ov();
         ovd = true;
@@ -659,11 +747,16 @@ DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT
       if (DTP_GRP_ZERO_MISSING && pending) zero_missing();
     };
     constexpr int MAXI = ((kGrpMax - 1) * NGF + NPOLL - 1) / NPOLL;
-    const int pi = (total + NPOLL - 1) / NPOLL;
-    if (pi <= 1) run(std::integral_constant<int, 1>{});
-    else if (pi <= 2) run(std::integral_constant<int, 2>{});
-    else if (pi <= 3) run(std::integral_constant<int, 3>{});
-    else run(std::integral_constant<int, MAXI>{});
+    if constexpr (GRC > 0) {  // the member count is a constant: so is the lane's item count
+      constexpr int pic = ((GRC - 1) * NG + NPOLL - 1) / NPOLL;
+      run(std::integral_constant<int, (pic <= 1 ? 1 : pic <= 3 ? pic : MAXI)>{});
+    } else {
+      const int pi = (total + NPOLL - 1) / NPOLL;
+      if (pi <= 1) run(std::integral_constant<int, 1>{});
+      else if (pi <= 2) run(std::integral_constant<int, 2>{});
+      else if (pi <= 3) run(std::integral_constant<int, 3>{});
+      else run(std::integral_constant<int, MAXI>{});
+    }
     if (prof) {
       prof->t_end = grp_clock();
       prof->polls = spins + 1;
@@ -674,7 +767,7 @@ DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT
   // 3. member-order sums
   if (DTP_GRP_SAME_XCD && !plain && !dead) {  // every member on this XCD: plain stores from the next exchange on
     bool same = true;
-    for (int r = 0; r < c.GR; ++r)
+    for (int r = 0; r < GR; ++r)
       if (r != c.k) same = same && __float_as_uint(peer[r * PS + P + 1]) == xcc;
     plain = same;
   }
@@ -682,7 +775,7 @@ DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT
 #pragma unroll
   for (int k = 0; k < NPT; ++k) acc[k] = 0.f;
   const int p0 = NPT * tid < P ? NPT * tid : 0;
-  for (int r = 0; r < c.GR; ++r) {
+  for (int r = 0; r < GR; ++r) {
     const float* row = peer + r * PS;
     const bool me = r == c.k;
 #pragma unroll
@@ -704,14 +797,27 @@ DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT
 // NG granules per member: the full payload (gradients, loss, XCC id) until every member is
 // known to share this XCD (plain), then without the XCC id, which has done its job: (P + 1)
 // floats (the CE head's 383 gradients + loss: 128 granules, 2 poll items per lane instead of 3)
-template <int P, int NPT, int NTHREADS, class OverlapFn>
+template <int P, int NPT, int NTHREADS, int GRC = 0, class OverlapFn>
 DTP_DEV float grp_allreduce_split3(const GrpCtx& c, int model, float (&g)[NPT], float loss, unsigned epoch, int tid,
                                    bool& dead, float* __restrict__ lds, unsigned xcc, bool& plain, GrpProf* prof,
                                    OverlapFn ov) {
   constexpr int NGF = grp_ng3(P), NGS = (P + 1 + 2) / 3;
   if (DTP_GRP_SAME_XCD && DTP_GRP_SHORT && NGS < NGF && plain)
-    return grp_allreduce_split3_ng<P, NPT, NTHREADS, NGS>(c, model, g, loss, epoch, tid, dead, lds, xcc, plain, prof, ov);
-  return grp_allreduce_split3_ng<P, NPT, NTHREADS, NGF>(c, model, g, loss, epoch, tid, dead, lds, xcc, plain, prof, ov);
+    return grp_allreduce_split3_ng<P, NPT, NTHREADS, NGS, GRC>(c, model, g, loss, epoch, tid, dead, lds, xcc, plain, prof,
+                                                               ov);
+  return grp_allreduce_split3_ng<P, NPT, NTHREADS, NGF, GRC>(c, model, g, loss, epoch, tid, dead, lds, xcc, plain, prof,
+                                                             ov);
+}
+
+// The same exchange published from payload-order rows (DTP_GRP_ROWS = 1; grp_allreduce_split3_ng's
+// RNW form): own() forms g and loss from the rows inside the exchange.
+template <int P, int NPT, int NTHREADS, int GRC, int RNW, int RSTRIDE, class OwnFn>
+DTP_DEV float grp_allreduce_rows3(const GrpCtx& c, int model, float (&g)[NPT], const float& loss, unsigned epoch,
+                                  int tid, bool& dead, float* __restrict__ lds, unsigned xcc, bool& plain,
+                                  GrpProf* prof, const float* __restrict__ rows, OwnFn own) {
+  static_assert(!DTP_GRP_SHORT, "the row form publishes the full payload");
+  return grp_allreduce_split3_ng<P, NPT, NTHREADS, grp_ng3(P), GRC, RNW, RSTRIDE>(
+      c, model, g, loss, epoch, tid, dead, lds, xcc, plain, prof, [] {}, rows, own);
 }
 
 #ifndef DTP_GRP_DIRECT3

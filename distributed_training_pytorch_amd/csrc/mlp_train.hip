@@ -611,12 +611,54 @@ DTP_DEV int lane_own_param(int s) {
   return p;
 }
 
-template <class S, int L, int NW, bool GRP = false>
+// payload float of dW tile cell (tile t, row, col): the torch-order parameter whose gradient
+// the cell holds (the inverse of lane_pos's tp), P for the loss cell, -1 for a cell of no one
+template <class S>
+DTP_HD constexpr int lane_row_slot(int t, int row, int col) {
+  using SC = Scal<S>;
+  for (int l = 0; l < S::NL; ++l) {
+    if (SC::tile(l) != t) continue;
+    const int j = row - SC::rowoff(l), i = col - SC::coloff(l), I = S::din(l);
+    if (j >= 0 && j < S::dout(l) && i >= 0 && i <= I) return i < I ? S::gw(l) + j * I + i : S::gb(l) + j;
+  }
+  if (t == SC::tile(S::NL - 1) && row == SC::lossrow() && col == SC::losscol()) return S::P;
+  return -1;
+}
+// the map is a bijection from the real tile cells onto [0, P], and sends the cell lane_pos
+// gives parameter p (tile(l), rowoff + j, coloff + i) back to p
+template <class S>
+constexpr bool lane_row_map_ok() {
+  using SC = Scal<S>;
+  int hits[S::P + 1] = {};
+  for (int t = 0; t < SC::NT; ++t)
+    for (int row = 0; row < 16; ++row)
+      for (int col = 0; col < 16; ++col) {
+        const int f = lane_row_slot<S>(t, row, col);
+        if (f > S::P) return false;
+        if (f >= 0) ++hits[f];
+      }
+  for (int f = 0; f <= S::P; ++f)
+    if (hits[f] != 1) return false;
+  for (int l = 0; l < S::NL; ++l)
+    for (int j = 0; j < S::dout(l); ++j)
+      for (int i = 0; i <= S::din(l); ++i) {
+        const int p = i < S::din(l) ? S::gw(l) + j * S::din(l) + i : S::gb(l) + j;
+        if (lane_row_slot<S>(SC::tile(l), SC::rowoff(l) + j, SC::coloff(l) + i) != p) return false;
+      }
+  return true;
+}
+
+// ROWS: the per-wave partial dW sums are parked in payload order (grp_core.h, DTP_GRP_ROWS):
+// one row of grp_row_floats(P) floats per wave, then one sink float per lane for the tile
+// cells that hold no parameter
+template <class S, int L, int NW, bool GRP = false, bool ROWS = false>
 struct LaneSmem {
   using C = LaneCfg<S, L>;
+  static constexpr int RSINK = grp_row_floats(S::P);  // a row's sink floats start here
+  static constexpr int RSTR = RSINK + kWave;          // row stride
   alignas(16) float wb[C::pad4(C::LW)];
   alignas(16) float stg[NW][lane_areas<S>()][2 * C::AREA];  // per wave, per area: dz operand, h operand
-  alignas(16) float red[NW][Scal<S>::NT * Scal<S>::TSZ];             // per-wave partial dW tiles
+  alignas(16) float red[NW][ROWS ? RSTR : Scal<S>::NT * Scal<S>::TSZ];  // per-wave partial dW tiles (or rows)
   alignas(16) float2 adam_tab[kAdamTab];
   alignas(16) float data[kLaneData];
   float sink[4];
@@ -638,7 +680,8 @@ struct LaneSmem {
 // optimizer step.
 // CE: softmax cross-entropy head (class ids as floats in Y) instead of MSE; MODE: Adam or
 // SGD (momentum, weight decay), local or with the in-kernel xGMI exchange.
-template <class S, int L, int MODE, bool PROF = false, int NW = 4, bool GRP = false, bool CE = false>
+// GRC > 0: the member count of the split-batch step as a constant (a.groups == GRC).
+template <class S, int L, int MODE, bool PROF = false, int NW = 4, bool GRP = false, bool CE = false, int GRC = 0>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4, NW / 4)))
 void mlp_train_lanes_kernel(DtpTrainArgs a) {
   using SC = Scal<S>;
@@ -657,7 +700,17 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   constexpr bool kXsplit = DTP_XGMI_SPLIT && NW == 4 && (MODE == DTP_MODE_XGMI_ADAM || MODE == DTP_MODE_XGMI_SGD);
   // the 3-float cross-GPU exchange (xgmi_core.h:xgmi_allreduce_g3), 4-wave instances
   constexpr bool kXg3 = DTP_XGMI_G3 && !kXsplit && NW == 4 && kXgmi;
-  __shared__ __align__(16) LaneSmem<S, L, NW, GRP || kXsplit || kXg3> sm;
+  // the split-batch members park their dW sums in payload-order rows (DTP_GRP_ROWS); the
+  // on-chip exchange publishes straight from them (1) or stages them as before (2)
+  constexpr bool kRows = GRP && DTP_GRP_ROWS != 0;
+  constexpr bool kRowsPub = kRows && DTP_GRP_ROWS == 1 && !kXgmi && DTP_GRP_SPLIT && DTP_GRP_G3;
+  static_assert(!kRows || !DTP_LANE_OWN, "the rows hold payload float f = ownership slot f in torch order");
+  static_assert(!kRows || (!DTP_GRP_DIRECT && !DTP_GRP_DIRECT3), "the direct A/B paths index the tile layout");
+  static_assert(!kRows || lane_row_map_ok<S>(), "tile cells -> payload floats: a bijection onto [0, P]");
+  static_assert(GRC == 0 || (GRP && !kXgmi && GRC >= 2 && GRC <= kGrpMax), "a constant member count: on-chip exchange");
+  constexpr int kLossPos = kRows ? grp_row_pos(P) : SC::losspos();  // a wave's loss in sm.red[wave]
+  using Smem = LaneSmem<S, L, NW, GRP || kXsplit || kXg3, kRows>;
+  __shared__ __align__(16) Smem sm;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int model = GRP ? (int)(blockIdx.x & 7u) : (int)blockIdx.x;
   const int gk = GRP ? (int)(blockIdx.x >> 3) : 0;  // member of the model's group
@@ -707,6 +760,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     const int p = DTP_LANE_OWN ? (own ? lane_own_param<S>(s_) : 0) : s_;
     pown[k] = p;
     lane_pos<C, S>(own ? p : 0, pf[k], pb[k], tp[k]);
+    if constexpr (kRows) tp[k] = own ? grp_row_pos(s_) : 0;  // its sums come from the rows
     pw[k] = own ? gp[p] : 0.f;
     mr[k] = own ? a.opt_m[(size_t)model * P + p] : 0.f;
     vr[k] = (kAdam && own) ? a.opt_v[(size_t)model * P + p] : 0.f;
@@ -738,6 +792,21 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       int pf_, pb_, t_;
       lane_pos<C, S>(f < P ? f : 0, pf_, pb_, t_);
       gt3[i] = f < P ? t_ : (f == P ? SC::losspos() : -1);
+    }
+  }
+  // row layout: where each of this lane's 4 NT accumulator elements is parked (its payload
+  // float's place in the wave's row, or the lane's sink float), fixed for the launch
+  int rp[kRows ? NT : 1][4];
+  if constexpr (kRows) {
+#pragma unroll
+    for (int tt = 0; tt < NT; ++tt) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int f = lane_row_slot<S>(tt, 4 * (lane >> 4) + e, lane & 15);
+        // bf16 MFMA tiles: the loss cell saw bf16-truncated values, the wave's fp32 loss is written instead
+        const bool real = f >= 0 && !(S::BF && DTP_LANES_BFMMA && f == P);
+        rp[tt][e] = real ? grp_row_pos(f) : Smem::RSINK + lane;
+      }
     }
   }
   const int t0 = a.host_t0 >= 0 ? a.host_t0 : a.step[model];
@@ -1023,15 +1092,24 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     DTP_STAMP(8 + wave);
     DTP_STAMP(3);
     {
-      const int q = lane >> 4, col = lane & 15;
+      if constexpr (kRows) {  // payload order: every element to its parameter's float (or the sink)
 #pragma unroll
-      for (int tt = 0; tt < NT; ++tt)
-        *reinterpret_cast<f32x4*>(&sm.red[wave][tt * SC::TSZ + SC::tslot(4 * q, col)]) = acc[tt];
+        for (int tt = 0; tt < NT; ++tt) {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) sm.red[wave][rp[tt][e]] = acc[tt][e];
+        }
+      } else {
+        const int q = lane >> 4, col = lane & 15;
+#pragma unroll
+        for (int tt = 0; tt < NT; ++tt)
+          *reinterpret_cast<f32x4*>(&sm.red[wave][tt * SC::TSZ + SC::tslot(4 * q, col)]) = acc[tt];
+      }
       if constexpr (S::BF && DTP_LANES_BFMMA) {
         // the bf16 MFMA saw the loss row's per-sample values truncated to bf16: the wave's
-        // loss goes in from a wave sum of the fp32 values instead (same LDS slot, written after)
+        // loss goes in from a wave sum of the fp32 values instead (same LDS slot, written after;
+        // row layout: the loss cell itself went to the sink)
         const float lw = wave_sum(p0 ? lpart : 0.f);
-        if (lane == 0) sm.red[wave][SC::losspos()] = lw;
+        if (lane == 0) sm.red[wave][kLossPos] = lw;
       }
     }
     __syncthreads();
@@ -1050,11 +1128,11 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       }
       float ls = 0.f;
 #pragma unroll
-      for (int ww = 0; ww < NW; ++ww) ls += sm.red[ww][SC::losspos()];
+      for (int ww = 0; ww < NW; ++ww) ls += sm.red[ww][kLossPos];
       lsum = ls;
     };
     // the split-batch step's direct publish forms these inside the exchange
-    constexpr bool kDefer = GRP && !kXgmi && DTP_GRP_SPLIT && DTP_GRP_G3 && DTP_GRP_DIRECT3;
+    constexpr bool kDefer = (GRP && !kXgmi && DTP_GRP_SPLIT && DTP_GRP_G3 && DTP_GRP_DIRECT3) || kRowsPub;
     if constexpr (!kDefer) own_sums();
     // the next step's sample and the index of the one after it (independent of this step's
     // exchange: the split-batch step runs it inside the exchange's waits)
@@ -1106,9 +1184,16 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
                                                 reinterpret_cast<float*>(sm.gx), xcc, gplain,
                                                 PROF ? &gp_ : nullptr, pub3, own_sums);
 #elif DTP_GRP_SPLIT && DTP_GRP_G3
-      lsum = grp_allreduce_split3<P, NPT, NTH>(gctx, model, g, lsum, xepoch, tid, xdead, reinterpret_cast<float*>(sm.gx),
-                                               xcc, gplain, PROF ? &gp_ : nullptr, next_sample);
-      sampled = DTP_GRP_OVERLAP;
+      if constexpr (kRowsPub) {  // published from the rows; own_sums runs inside (wave order: the same bits)
+        lsum = grp_allreduce_rows3<P, NPT, NTH, GRC, NW, Smem::RSTR>(gctx, model, g, lsum, xepoch, tid, xdead,
+                                                                     reinterpret_cast<float*>(sm.gx), xcc, gplain,
+                                                                     PROF ? &gp_ : nullptr, &sm.red[0][0], own_sums);
+      } else {
+        lsum = grp_allreduce_split3<P, NPT, NTH, GRC>(gctx, model, g, lsum, xepoch, tid, xdead,
+                                                      reinterpret_cast<float*>(sm.gx), xcc, gplain,
+                                                      PROF ? &gp_ : nullptr, next_sample);
+        sampled = DTP_GRP_OVERLAP;
+      }
 #elif DTP_GRP_SPLIT
       lsum = grp_allreduce_split<P, NPT, NTH>(gctx, model, g, lsum, xepoch, tid, xdead, sm.gx,
                                               sm.gx + xgmi_slot16(P, NPT), xcc, gplain, PROF ? &gp_ : nullptr);
@@ -1291,10 +1376,19 @@ void launch_lanes(const DtpTrainArgs& a, hipStream_t st) {
 }
 
 // split-batch step: member k of model m is block m + 8 k (blocks of absent models exit)
-template <class S, int L, int NW, bool PROF = false, int MODE = DTP_MODE_ADAM, bool CE = false>
+// (GRC > 0: the instance with a.groups == GRC members as a constant)
+template <class S, int L, int NW, bool PROF = false, int MODE = DTP_MODE_ADAM, bool CE = false, int GRC = 0>
 void launch_lanes_grp(const DtpTrainArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL((dtp::mlp_train_lanes_kernel<S, L, MODE, PROF, NW, true, CE>), dim3(8 * a.groups),
+  hipLaunchKernelGGL((dtp::mlp_train_lanes_kernel<S, L, MODE, PROF, NW, true, CE, GRC>), dim3(8 * a.groups),
                      dim3(64 * NW), 0, st, a);
+}
+
+// the on-chip split-batch instance of gr members: 4 members (batch 256 on one rank) have the
+// count as a constant (DTP_GRP_GRC), every other count reads it from the arguments
+template <class S, int MODE, bool CE = false>
+TrainLaunchFn grp_members(int gr) {
+  if (DTP_GRP_GRC && gr == 4) return &launch_lanes_grp<S, 4, 4, false, MODE, CE, 4>;
+  return &launch_lanes_grp<S, 4, 4, false, MODE, CE>;
 }
 
 // the lanes instances of one (shape, L, NW, loss, optimizer family)
@@ -1344,7 +1438,7 @@ TrainLaunchFn lanes_inst(int in, int h, int nl, int out, int L, int NW, int mode
 
 // Instances of the split-batch step (4-lanes members; one rank, or several with the flat
 // xGMI exchange): toy fp32 with Adam or SGD, toy bf16 with Adam, the CE head with Adam or SGD
-TrainLaunchFn grp_inst(int in, int h, int nl, int out, int mode, bool ce, bool bf16) {
+TrainLaunchFn grp_inst(int in, int h, int nl, int out, int mode, bool ce, bool bf16, int gr) {
   const bool toy = in == 2 && h == 10 && nl == 5 && out == 1;
   const bool ce4 = in == 2 && h == 10 && nl == 5 && out == 4;
   using T = dtp::Stage<2, 10, 5, 1, false>;
@@ -1355,21 +1449,21 @@ TrainLaunchFn grp_inst(int in, int h, int nl, int out, int mode, bool ce, bool b
   const bool xg = mode == DTP_MODE_XGMI_ADAM || mode == DTP_MODE_XGMI_SGD;
   if (bf16) {
     if (!toy || ce || sgd) return nullptr;
-    return xg ? &launch_lanes_grp<B, 4, 4, false, DTP_MODE_XGMI_ADAM> : &launch_lanes_grp<B, 4, 4>;
+    return xg ? &launch_lanes_grp<B, 4, 4, false, DTP_MODE_XGMI_ADAM> : grp_members<B, DTP_MODE_ADAM>(gr);
   }
   if (ce) {
     if (!ce4) return nullptr;
     switch (mode) {
-      case DTP_MODE_ADAM: return &launch_lanes_grp<C4, 4, 4, false, DTP_MODE_ADAM, true>;
-      case DTP_MODE_SGD: return &launch_lanes_grp<C4, 4, 4, false, DTP_MODE_SGD, true>;
+      case DTP_MODE_ADAM: return grp_members<C4, DTP_MODE_ADAM, true>(gr);
+      case DTP_MODE_SGD: return grp_members<C4, DTP_MODE_SGD, true>(gr);
       case DTP_MODE_XGMI_ADAM: return &launch_lanes_grp<C4, 4, 4, false, DTP_MODE_XGMI_ADAM, true>;
       default: return &launch_lanes_grp<C4, 4, 4, false, DTP_MODE_XGMI_SGD, true>;
     }
   }
   if (!toy) return nullptr;
   switch (mode) {
-    case DTP_MODE_ADAM: return &launch_lanes_grp<T, 4, 4>;
-    case DTP_MODE_SGD: return &launch_lanes_grp<T, 4, 4, false, DTP_MODE_SGD>;
+    case DTP_MODE_ADAM: return grp_members<T, DTP_MODE_ADAM>(gr);
+    case DTP_MODE_SGD: return grp_members<T, DTP_MODE_SGD>(gr);
     case DTP_MODE_XGMI_ADAM: return &launch_lanes_grp<T, 4, 4, false, DTP_MODE_XGMI_ADAM>;
     default: return &launch_lanes_grp<T, 4, 4, false, DTP_MODE_XGMI_SGD>;
   }
@@ -1475,7 +1569,7 @@ TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int ou
       }
     }
     if (gr > 1) {
-      if (TrainLaunchFn f = grp_inst(in, h, nl, out, mode, ce, a.bf16)) {
+      if (TrainLaunchFn f = grp_inst(in, h, nl, out, mode, ce, a.bf16, gr)) {
         if (pick) *pick = LanePick{4, 4, gr};
         return f;
       }
@@ -1678,7 +1772,11 @@ int dtp_train_engine_profile(void* h, int n_steps, int t0, void* prof, void* str
   a.n_steps = n_steps;
   a.host_t0 = t0;
   a.status = static_cast<int*>(prof);
-  launch_lanes_grp<dtp::Stage<2, 10, 5, 1, false>, 4, 4, true>(a, (hipStream_t)stream);
+  // the instance the engine runs: 4 members as a constant (DTP_GRP_GRC), else the run-time count
+  if (DTP_GRP_GRC && e->pick.GR == 4 && e->pick.NW == 4)
+    launch_lanes_grp<dtp::Stage<2, 10, 5, 1, false>, 4, 4, true, DTP_MODE_ADAM, false, 4>(a, (hipStream_t)stream);
+  else
+    launch_lanes_grp<dtp::Stage<2, 10, 5, 1, false>, 4, 4, true>(a, (hipStream_t)stream);
   return check_launch("mlp_train_lanes_kernel<grp, prof>");
 }
 
