@@ -449,7 +449,12 @@ def bf16_round(t: torch.Tensor) -> torch.Tensor:
 def mlp_forward_ref_bf16(flat: torch.Tensor, spec: MlpSpec, x: torch.Tensor) -> torch.Tensor:
     """PyTorch reference of the bf16-compute kernels (fp32 tensors holding bf16 values:
     bf16 operands, fp32 accumulation, bf16 rounding of every matmul output and
-    activation) -- differentiable, its backward rounds the gradients the same way."""
+    activation) -- differentiable, its backward rounds the gradients the kernels round:
+    those of the matmul outputs and activations.  The weight and bias gradients are fp32
+    sums the kernels hand to the optimizer unrounded, so the gradient of a rounded
+    parameter passes through as it is (rounding it too put the model 2^-9 .. 2^-8 from the
+    kernels' gradient, which otherwise agree with it to fp32 accuracy:
+    tests/test_step_matrix_gpu.py)."""
     class _R(torch.autograd.Function):
         @staticmethod
         def forward(ctx, t):
@@ -459,10 +464,19 @@ def mlp_forward_ref_bf16(flat: torch.Tensor, spec: MlpSpec, x: torch.Tensor) -> 
         def backward(ctx, g):
             return bf16_round(g)
 
+    class _RP(torch.autograd.Function):  # a parameter: bf16 operand, fp32 gradient
+        @staticmethod
+        def forward(ctx, t):
+            return bf16_round(t)
+
+        @staticmethod
+        def backward(ctx, g):
+            return g
+
     ps = unflatten(flat, spec)
     h = _R.apply(x)
     for l in range(spec.n_layers):
-        h = _R.apply(F.linear(h, _R.apply(ps[2 * l]), _R.apply(ps[2 * l + 1])))
+        h = _R.apply(F.linear(h, _RP.apply(ps[2 * l]), _RP.apply(ps[2 * l + 1])))
         if spec.act(l):
             h = _R.apply(F.leaky_relu(h, spec.slope))
     return h
