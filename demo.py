@@ -16,6 +16,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from argument_parser import get_args  # noqa: E402
 from distributed_training_pytorch_amd.engine import runner  # noqa: E402
 from distributed_training_pytorch_amd.runtime.errors import record  # noqa: E402
+from distributed_training_pytorch_amd.utils.logging import rank_print  # noqa: E402
 
 
 @record
@@ -31,7 +32,7 @@ def main(argv=None):
     env, device, rank, world = runner.setup(config)
     summary = runner.train(config, env, device, rank, world, group="base-demo")
     if rank == 0:
-        print(f"[Process {rank}] summary: {summary}", flush=True)
+        rank_print(rank, f"summary: {summary}")  # one write: a test parses this line off a pipe all ranks share
     runner.teardown()
     return summary
 

@@ -160,7 +160,7 @@ def main(argv=None):
     summary.update({"stages": len(devs), "microbatches": config.microbatches})
     rank_print(rank, "Finished")
     if rank == 0:
-        print(f"[Process {rank}] summary: {summary}", flush=True)
+        rank_print(rank, f"summary: {summary}")
     runner.teardown()
     return summary
 

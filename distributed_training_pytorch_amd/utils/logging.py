@@ -14,6 +14,7 @@ from __future__ import annotations
 import json
 import math
 import os
+import sys
 import time
 from pathlib import Path
 
@@ -130,7 +131,12 @@ class MetricLogger:
 
 
 def rank_print(rank: int, *msg) -> None:
-    print(f"[Process {rank}]", *msg, flush=True)
+    """One line, written in ONE call: the ranks of a job share a pipe, and on an unbuffered
+    stream (PYTHONUNBUFFERED) ``print`` hands over its arguments and the newline piece by
+    piece, so that another rank's text lands inside the line (a pipe write of up to PIPE_BUF
+    bytes is atomic)."""
+    sys.stdout.write(" ".join([f"[Process {rank}]", *map(str, msg)]) + "\n")
+    sys.stdout.flush()
 
 
 class LossRing:

@@ -44,6 +44,18 @@ def test_fused_mlp_bf16_matches_rounding_model():
     torch.testing.assert_close(xd.grad.cpu(), xr.grad, rtol=3e-2, atol=3e-2)
     # and it really is bf16 compute: the output values are bf16-representable
     assert torch.equal(out.detach().bfloat16().float(), out.detach())
+    # and to the stage matrix's bound (tests/stage_cases.py): per quantity, nearer the rounding
+    # model than fp32 compute is by at least half of their distance D, both in fp64
+    from . import stage_cases as st
+
+    r64 = st.reference(TOY_SPEC, flat, x, go, torch.float64)
+    rb = st.reference(TOY_SPEC, flat, x, go, torch.float64, bf16=True)
+    D = st.errors(TOY_SPEC, rb, r64)
+    E = st.errors(TOY_SPEC, {"out": out.detach().cpu(), "grad_params": g, "grad_in": xd.grad.cpu()}, rb)
+    for names in (st.tensor_names(TOY_SPEC), ["out"], ["grad_in"]):
+        e, d = max(E[n] for n in names), max(D[n] for n in names)
+        print(f"BF16_STAGE {names[0]}: E {e:.3e} D {d:.3e}")
+        assert e <= d / 2, (names[0], e, d)
 
 
 def test_toy_model_under_autocast_runs_bf16_kernels():
