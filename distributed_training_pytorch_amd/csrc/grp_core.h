@@ -136,6 +136,25 @@ DTP_DEV uint32_t grp_hash3(uint32_t a, uint32_t b, uint32_t c) {
 // the per-step dispatch between the poll-loop variants is gone
 #define DTP_GRP_GRC 1
 #endif
+#ifndef DTP_GRP_DIET
+// The 3-float exchange and the lanes step's tail with fewer instructions on the serial path
+// behind the backward (one wave per SIMD: every instruction is an issue slot).  The same
+// floating-point operations in the same order, the same loads, stores and barriers; one bit
+// per item, 0 restores the earlier code:
+//   1: member-order sums without a branch per member: every thread writes its own sums into
+//      its own member's row, then reads all GR rows (aligned 8-byte reads for 2 parameters)
+//   2: the weight scatter after the optimizer writes through per-launch LDS offsets (a
+//      thread's unowned slots point at the sink floats)
+//   4: the exchange addresses of parity 0 are per-launch values, the parity's half of the
+//      buffer is the scalar offset operand of the buffer loads and stores
+//   8: plain as a wave-uniform scalar: the store's aux choice is one scalar branch
+//  (16 was a poll loop run by the wave for the constant-count instance: it gained alone, 3.04
+//      vs 3.09 us/step, lost on top of the others, 2.94 vs 2.90, and was taken out again;
+//      docs/perf_notes.md, profiles/step_diet/)
+//  32: the loss-log offset is a running 32-bit value, its store is guarded by one per-launch
+//      predicate, the Adam-table refill is counted down
+#define DTP_GRP_DIET (1 | 2 | 4 | 8 | 32)
+#endif
 // a payload-order row: granule q = floats [4q, 4q + 3), one pad float (aligned 16-byte reads)
 DTP_HD constexpr int grp_row_pos(int f) { return 4 * (f / 3) + f % 3; }
 DTP_HD constexpr int grp_row_floats(int P) { return 4 * grp_ng3(P); }
@@ -546,7 +565,16 @@ DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT
   static_assert(NTHREADS > kWave, "one publisher wave and at least one poller wave");
   float* const pub = lds;
   float* const peer = lds + PS;  // peer[r * PS + i]: member r's float i
-  const size_t base = (size_t)((int)(epoch & 1u) * c.n_models + model) * GR;
+  // DTP_GRP_DIET & 4: base addresses parity 0 (per-launch values once inlined in the step
+  // loop), the parity's half of the buffer goes into the accesses' scalar offset
+  constexpr bool kAddr = (DTP_GRP_DIET & 4) != 0;
+  const int par = kAddr ? __builtin_amdgcn_readfirstlane((int)(epoch & 1u)) : (int)(epoch & 1u);
+  const int soff = kAddr && par ? c.n_models * GR * slot * 16 : 0;
+  const size_t base = kAddr ? (size_t)0 : (size_t)(par * c.n_models + model) * GR;
+  auto goff = [&](int r, int q) {  // byte offset of granule q of member r
+    if constexpr (kAddr) return ((model * GR + r) * slot + q) * 16;
+    else return (int)(((base + r) * slot + q) * 16);
+  };
   // 1. the payload into LDS
   if constexpr (!kRows) {
 #pragma unroll
@@ -599,15 +627,18 @@ DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT
         v[j][2] = pub[3 * q + 2];
       }
     }
+    // plain is the same on every lane of wave 0 (decided from the same LDS words; the
+    // publisher never polls, so never times out): DTP_GRP_DIET & 8 tells the compiler
+    const bool pst = (DTP_GRP_DIET & 8) ? __builtin_amdgcn_readfirstlane((int)plain) != 0 : plain;
 #pragma unroll
     for (int j = 0; j < MAXJ; ++j) {
       const int q = tid + j * kWave;
       if (q < NG) {
         const uint32_t x0 = __float_as_uint(v[j][0]), x1 = __float_as_uint(v[j][1]), x2 = __float_as_uint(v[j][2]);
         const u32x4 qq = {epoch ^ grp_hash3(x0, x1, x2), x0, x1, x2};
-        const int off = (int)(((base + c.k) * slot + q) * 16);
-        if (DTP_GRP_SAME_XCD && plain) __builtin_amdgcn_raw_buffer_store_b128(qq, rs, off, 0, 0);
-        else __builtin_amdgcn_raw_buffer_store_b128(qq, rs, off, 0, DTP_GRP_ST_AUX);
+        const int off = goff(c.k, q);
+        if (DTP_GRP_SAME_XCD && pst) __builtin_amdgcn_raw_buffer_store_b128(qq, rs, off, soff, 0);
+        else __builtin_amdgcn_raw_buffer_store_b128(qq, rs, off, soff, DTP_GRP_ST_AUX);
       }
     }
     if (prof) {
@@ -654,14 +685,14 @@ DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT
         const int ri = i / NG, q = i - ri * NG;
         const int r = ri < c.k ? ri : ri + 1;
         const bool in = i < total;
-        off[j] = in ? (int)(((base + r) * slot + q) * 16) : 0;
+        off[j] = in ? goff(r, q) : 0;
         dst[j] = r * PS + 3 * q;
         if (in) pending |= 1u << j;
       }
       auto issue = [&](u32x4 (&x)[PI]) {
         asm volatile("" ::: "memory");  // a poll is never merged with, or hoisted above, an earlier one
 #pragma unroll
-        for (int j = 0; j < PI; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, off[j], 0, DTP_GRP_LD_AUX);
+        for (int j = 0; j < PI; ++j) x[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, off[j], soff, DTP_GRP_LD_AUX);
       };
       auto consume = [&](const u32x4 (&x)[PI]) {
 #pragma unroll
@@ -775,12 +806,41 @@ DTP_DEV float grp_allreduce_split3_ng(const GrpCtx& c, int model, float (&g)[NPT
 #pragma unroll
   for (int k = 0; k < NPT; ++k) acc[k] = 0.f;
   const int p0 = NPT * tid < P ? NPT * tid : 0;
-  for (int r = 0; r < GR; ++r) {
-    const float* row = peer + r * PS;
-    const bool me = r == c.k;
+  if constexpr ((DTP_GRP_DIET & 1) != 0) {
+    // every thread puts its own sums into its own member's row -- no poller writes row c.k,
+    // and a thread reads back only what it wrote itself (the LDS queue is in order); a slot
+    // it does not own goes to the row's XCC float, which nobody reads in the own row -- then
+    // all GR rows are read alike.  The same additions in the same member order.
+    // Some of these reads return values nobody defined, and every one of them is discarded:
+    // the own row's loss float row[P] is never written (rl gives way to loss in the select
+    // below; the last owner of an odd P also gets it as its second float, a slot it does not
+    // own), and a thread past the owners (p0 = 0) reads floats 0 and 1 of the own row while
+    // thread 0 writes them.  The sums of unowned slots end in the optimizer's unowned
+    // registers, whose weights go to the sink.  The unowned stores all hit float P + 1.
+    float* const mine = peer + c.k * PS;
 #pragma unroll
-    for (int k = 0; k < NPT; ++k) acc[k] += me ? g[k] : row[p0 + k];
-    lacc += me ? loss : row[P];
+    for (int k = 0; k < NPT; ++k) mine[NPT * tid + k < P ? NPT * tid + k : P + 1] = g[k];
+    for (int r = 0; r < GR; ++r) {
+      const float* row = peer + r * PS;
+      if constexpr (NPT == 2 && PS % 2 == 0) {
+        const float2 t = *reinterpret_cast<const float2*>(row + p0);
+        acc[0] += t.x;
+        acc[1] += t.y;
+      } else {
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) acc[k] += row[p0 + k];
+      }
+      const float rl = row[P];
+      lacc += r == c.k ? loss : rl;
+    }
+  } else {
+    for (int r = 0; r < GR; ++r) {
+      const float* row = peer + r * PS;
+      const bool me = r == c.k;
+#pragma unroll
+      for (int k = 0; k < NPT; ++k) acc[k] += me ? g[k] : row[p0 + k];
+      lacc += me ? loss : row[P];
+    }
   }
 #pragma unroll
   for (int k = 0; k < NPT; ++k) g[k] = acc[k];

@@ -708,6 +708,8 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   static_assert(!kRows || (!DTP_GRP_DIRECT && !DTP_GRP_DIRECT3), "the direct A/B paths index the tile layout");
   static_assert(!kRows || lane_row_map_ok<S>(), "tile cells -> payload floats: a bijection onto [0, P]");
   static_assert(GRC == 0 || (GRP && !kXgmi && GRC >= 2 && GRC <= kGrpMax), "a constant member count: on-chip exchange");
+  // the per-step tail of the on-chip split-batch instances with fewer instructions (DTP_GRP_DIET)
+  constexpr bool kDiet = GRP && !kXgmi && DTP_GRP_SPLIT && DTP_GRP_G3 && DTP_GRP_DIET != 0;
   constexpr int kLossPos = kRows ? grp_row_pos(P) : SC::losspos();  // a wave's loss in sm.red[wave]
   using Smem = LaneSmem<S, L, NW, GRP || kXsplit || kXg3, kRows>;
   __shared__ __align__(16) Smem sm;
@@ -834,6 +836,9 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   roll(e2, b2);
   int fidx = fast_index(e2, b2);
   unsigned xepoch = kXgmi ? a.epoch[model] : (GRP ? a.grp_epoch[model] : 0u);  // GRP + xGMI: the xGMI epochs
+  // one model per workgroup: the epoch is the same on every lane (its parity selects the
+  // exchange buffer's half through a scalar offset, grp_core.h)
+  if constexpr (kDiet && (DTP_GRP_DIET & 4)) xepoch = (unsigned)__builtin_amdgcn_readfirstlane((int)xepoch);
   // the exchanges' sticky timeout flag, read once per launch with the prologue loads
   const int* xst = kXgmi ? a.status : (GRP ? a.grp_status : nullptr);
   bool xdead = xst ? (__hip_atomic_load(xst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) : false;
@@ -868,7 +873,27 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     }
   }
   stamp_launch(22);
+  // DTP_GRP_DIET & 2: where the weight scatter after the optimizer writes, as float offsets
+  // into sm, fixed for the launch: the parameter's forward and backward copies, or the sink
+  // floats for a slot this thread does not own (the last owner of an odd P owns one of two)
+  // or a parameter without a backward copy
+  constexpr int kSinkOff = (int)(offsetof(Smem, sink) / sizeof(float));
+  static_assert(offsetof(Smem, wb) == 0, "the scatter offsets count from sm.wb");
+  int wo[NPT][2];
+#pragma unroll
+  for (int k = 0; k < NPT; ++k) {
+    const bool own = NPT * tid + k < P;
+    wo[k][0] = own ? pf[k] : kSinkOff;
+    wo[k][1] = own && pb[k] >= 0 ? pb[k] : kSinkOff + 1;
+  }
   int lslot = a.loss_log ? t0 % a.loss_log_cap : 0;
+  // DTP_GRP_DIET & 32: the loss log as a running element offset (lslot * n_models + model,
+  // advanced by n_models per step, wrapped at the ring's end), one per-launch predicate for
+  // its store, and the Adam table's refill counted down
+  const bool llog = tid == ((kXgmi || GRP) ? xgmi_loss_tid<NPT>(P, NTH) : 0) && a.loss_log && lead;
+  const int lend = a.loss_log ? a.loss_log_cap * a.n_models : a.n_models;
+  int loff = lslot * a.n_models + model;
+  int refill = kAdamTab;
   auto fast_gather = [&](int di, float (&x)[S::IN], float (&y)[S::OUT]) {
     const bool v = di >= 0;
     di = (unsigned)di < (unsigned)smp.n ? di : 0;
@@ -1139,7 +1164,9 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     const int lslot_now = lslot;
     auto next_sample = [&]() {
       roll(epoch, bi);
-      if (a.loss_log && ++lslot == a.loss_log_cap) lslot = 0;
+      if constexpr (!(kDiet && (DTP_GRP_DIET & 32))) {
+        if (a.loss_log && ++lslot == a.loss_log_cap) lslot = 0;
+      }
       nvalid = fast_gather(fidx, nx, ny);
       roll(e2, b2);
       fidx = fast_index(e2, b2);
@@ -1248,19 +1275,35 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       for (int k = 0; k < NPT; ++k) {
         const bool own = NPT * tid + k < P;
         const float wv = S::rnd(pw[k]);
-        *(own ? &sm.wb[pf[k]] : &sm.sink[0]) = wv;
-        *(own && pb[k] >= 0 ? &sm.wb[pb[k]] : &sm.sink[1]) = wv;
+        if constexpr (kDiet && (DTP_GRP_DIET & 2)) {
+          float* const smf = reinterpret_cast<float*>(&sm);
+          smf[wo[k][0]] = wv;
+          smf[wo[k][1]] = wv;
+        } else {
+          *(own ? &sm.wb[pf[k]] : &sm.sink[0]) = wv;
+          *(own && pb[k] >= 0 ? &sm.wb[pb[k]] : &sm.sink[1]) = wv;
+        }
       }
     }
     // the thread that holds the summed loss logs it (the loss granule's owner: every other
     // thread of a split-batch member only has its own member's share)
-    if (tid == ((kXgmi || GRP) ? xgmi_loss_tid<NPT>(P, NTH) : 0) && a.loss_log && lead) {
+    if constexpr (kDiet && (DTP_GRP_DIET & 32)) {
+      if (llog) a.loss_log[loff] = kXgmi ? gloss * a.hp.grad_scale : mean_loss;
+      loff += a.n_models;
+      loff = loff >= lend ? loff - lend : loff;
+    } else if (tid == ((kXgmi || GRP) ? xgmi_loss_tid<NPT>(P, NTH) : 0) && a.loss_log && lead) {
       const float lg = kXgmi ? gloss * a.hp.grad_scale : mean_loss;
       a.loss_log[(size_t)lslot_now * a.n_models + model] = lg;
     }
     DTP_STAMP(6);
     __syncthreads();
-    if (kAdam && (it + 1) % kAdamTab == 0 && it + 1 < a.n_steps) {
+    if constexpr (kDiet && (DTP_GRP_DIET & 32)) {
+      if (kAdam && --refill == 0 && it + 1 < a.n_steps) {
+        refill = kAdamTab;
+        fill_adam(it + 1);
+        __syncthreads();
+      }
+    } else if (kAdam && (it + 1) % kAdamTab == 0 && it + 1 < a.n_steps) {
       fill_adam(it + 1);
       __syncthreads();
     }
@@ -1509,6 +1552,8 @@ int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow, bool fast1) 
   const int want = env >= 0 ? env : (a.groups > 0 ? 1 : (a.groups < 0 ? 0 : -1));
   if (!allow || want == 0 || forced_lanes || a.n_models > 8) return 1;
   if (a.smp.n * (in + out) > dtp::kLaneData) return 1;
+  // the split-batch step keeps its loss-log position as a 32-bit element offset (DTP_GRP_DIET)
+  if (a.loss_log && (long long)a.loss_log_cap * a.n_models > 0x7fff0000LL) return 1;
   const int b = min(a.smp.batch, a.smp.num_samples);
   if (b <= 64) return 1;
   const int gr = (b + 63) / 64;
