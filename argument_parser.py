@@ -36,6 +36,17 @@ def build_parser(description: str | None = None) -> argparse.ArgumentParser:
                            "(torch.nn.utils.clip_grad_norm_ per optimizer; the module engine's flat kernel does it)")
     clip.add_argument("--clip_grad_value", type=float, default=0.0,
                       help="> 0: clamp every gradient element to [-F, F] before the optimizer step")
+    p.add_argument("--lr_schedule", choices=["constant", "linear", "cosine", "step"], default="constant",
+                   help="learning rate of step t: --lr (t+1)/--warmup_iters during warm-up, then constant, a "
+                        "linear or cosine decay to --lr_min_ratio x --lr at --lr_decay_iters, or x --lr_gamma "
+                        "every --lr_step_size steps; read by the kernels from tables formed once (no host work per "
+                        "step in persistent launches and flat-optimizer graph replays); the defaults are the "
+                        "fixed --lr")
+    p.add_argument("--warmup_iters", type=int, default=0, help="linear warm-up steps (0: none)")
+    p.add_argument("--lr_decay_iters", type=int, default=None, help="step at which the decay ends (default: --iters)")
+    p.add_argument("--lr_min_ratio", type=float, default=0.0, help="final rate of linear / cosine as a share of --lr")
+    p.add_argument("--lr_step_size", type=int, default=None, help="--lr_schedule step: steps between decays")
+    p.add_argument("--lr_gamma", type=float, default=0.1, help="--lr_schedule step: factor of each decay")
     p.add_argument("--eval_every", type=int, default=0,
                    help="> 0: evaluate both models on a held-out set after every K-th iteration and after the "
                         "last one (val/lossX, val/lossY; val/accX, val/accY with --loss ce); 0 = off")

@@ -131,7 +131,8 @@ def main(argv=None):
     ds = ToyData(n=config.n_samples, seed=config.seed, rank=rank, per_rank=config.per_rank_data)
     geom = SamplerGeometry(n=config.n_samples, world=world, rank=rank, batch=config.batch_size,
                            distributed=config.dataloader == "distributed", seed=0)
-    ocfg = OptimConfig(config.optimizer, config.lr, momentum=config.momentum, weight_decay=config.weight_decay)
+    ocfg = OptimConfig(config.optimizer, config.lr, momentum=config.momentum, weight_decay=config.weight_decay,
+                       schedule=runner.lr_schedule(config))
     logger = MetricLogger(project=config.project, group="multi-gpu-per-node", log_dir=config.log_dir, rank=rank)
     faults = FaultInjector(config.fail_at_iter, config.fail_rank, rank)
     pbar = runner._progress(rank, config.iters, config)
@@ -158,6 +159,7 @@ def main(argv=None):
         pbar.close()
     logger.finish()
     summary.update({"stages": len(devs), "microbatches": config.microbatches})
+    summary.update(runner._lr_summary(config, int(summary.get("iters", config.iters))))
     rank_print(rank, "Finished")
     if rank == 0:
         rank_print(rank, f"summary: {summary}")

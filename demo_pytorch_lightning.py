@@ -18,6 +18,7 @@ import torch  # noqa: E402
 import torch.nn as nn  # noqa: E402
 from torch.utils.data import DataLoader  # noqa: E402
 
+from distributed_training_pytorch_amd.engine import runner  # noqa: E402
 from distributed_training_pytorch_amd.ops.loss import MSELoss  # noqa: E402
 from distributed_training_pytorch_amd.runtime import bootstrap  # noqa: E402
 from distributed_training_pytorch_amd.runtime.errors import record  # noqa: E402
@@ -26,12 +27,13 @@ from toy_model_and_data import ToyData, ToyModel  # noqa: E402
 
 
 class LitToyModel(LightningModule):
-    def __init__(self, lr: float = 1e-3):
+    def __init__(self, lr: float = 1e-3, schedule=None):
         super().__init__()
         self.model_X = ToyModel()
         self.model_Y = ToyModel()
         self.loss = MSELoss()  # nn.MSELoss drop-in: one fused launch each way (ops/loss.py)
         self.lr = lr
+        self.schedule = schedule  # ops.schedule.LrSchedule or None: the rate of every optimizer step
 
     def forward(self, x):
         # both models on the same batch: one fused forward launch on the GPU (models/toy.py)
@@ -63,8 +65,18 @@ class LitToyModel(LightningModule):
                 "val_metrics": ["val_loss_X", "val_loss_Y"]}
 
     def configure_optimizers(self):
-        return [torch.optim.Adam(self.model_X.parameters(), lr=self.lr),
-                torch.optim.Adam(self.model_Y.parameters(), lr=self.lr)]
+        if self.schedule is None:
+            return [torch.optim.Adam(self.model_X.parameters(), lr=self.lr),
+                    torch.optim.Adam(self.model_Y.parameters(), lr=self.lr)]
+        # --lr_schedule: LambdaLR over the schedule's values at step interval (base rate 1.0, so
+        # the param group's lr is the value itself); the in-repo Trainer tabulates it and the
+        # kernels read the table by their step counter
+        out = []
+        for m in (self.model_X, self.model_Y):
+            opt = torch.optim.Adam(m.parameters(), lr=1.0)
+            sched = torch.optim.lr_scheduler.LambdaLR(opt, self.schedule.lr)
+            out.append({"optimizer": opt, "lr_scheduler": {"scheduler": sched, "interval": "step"}})
+        return tuple(out)
 
 
 def get_args(argv=None):
@@ -101,6 +113,14 @@ def get_args(argv=None):
                       help="Trainer(gradient_clip_val=F, gradient_clip_algorithm='norm'): per optimizer, before its step")
     clip.add_argument("--clip_grad_value", type=float, default=0.0,
                       help="Trainer(gradient_clip_val=F, gradient_clip_algorithm='value')")
+    p.add_argument("--lr", type=float, default=1e-3)
+    p.add_argument("--lr_schedule", choices=["constant", "linear", "cosine", "step"], default="constant",
+                   help="configure_optimizers returns a step-interval LambdaLR over this schedule (argument_parser.py)")
+    p.add_argument("--warmup_iters", type=int, default=0)
+    p.add_argument("--lr_decay_iters", type=int, default=None, help="default: --steps")
+    p.add_argument("--lr_min_ratio", type=float, default=0.0)
+    p.add_argument("--lr_step_size", type=int, default=None)
+    p.add_argument("--lr_gamma", type=float, default=0.1)
     return p.parse_args(argv)
 
 
@@ -112,7 +132,8 @@ def main(argv=None):
     torch.manual_seed(a.seed)
     ds = ToyData(seed=a.seed)
     dl = DataLoader(ds, batch_size=a.batch_size, pin_memory=torch.cuda.is_available(), num_workers=a.num_workers)
-    model = LitToyModel()
+    a.iters = a.steps  # the schedule's default length, as --iters is for the other entry points
+    model = LitToyModel(lr=a.lr, schedule=runner.lr_schedule(a))
     accel = a.accelerator or ("gpu" if torch.cuda.is_available() else "cpu")
     TrainerCls = Trainer
     if a.use_lightning:

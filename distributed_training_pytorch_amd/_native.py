@@ -60,6 +60,9 @@ class Hyper(ctypes.Structure):
         ("momentum", c_double),
         ("slope", c_float),
         ("grad_scale", c_float),
+        ("lr_tab", c_void_p),     # float64 [lr_tab_len] on the device (ops.schedule), or null: lr
+        ("lr_tab_len", c_int),
+        ("pad_", c_int),
     ]
 
 

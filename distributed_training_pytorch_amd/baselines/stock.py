@@ -23,7 +23,9 @@ def plain_toy_model(slope: float = 0.01) -> nn.Module:
 
 class StockLoop:
     def __init__(self, dataset, device, batch: int = 256, seed: int = 0, ddp: bool = True,
-                 clip_grad_norm: float = 0.0, clip_grad_value: float = 0.0):
+                 clip_grad_norm: float = 0.0, clip_grad_value: float = 0.0, schedule=None):
+        """``schedule``: an ``ops.schedule.LrSchedule``; both Adams then follow its values
+        through ``torch.optim.lr_scheduler.LambdaLR`` (stepped after every optimizer step)."""
         torch.manual_seed(seed)
         # gradient clipping per model (= per optimizer), torch's own functions; 0 = off
         self.clip_grad_norm = clip_grad_norm
@@ -38,6 +40,13 @@ class StockLoop:
             self.my = DDP(self.my, device_ids=ids)
         self.ox = torch.optim.Adam(self.mx.parameters(), lr=1e-3)
         self.oy = torch.optim.Adam(self.my.parameters(), lr=1e-3)
+        self.schedulers = []
+        if schedule is not None:
+            # base lr 1.0 x the table's value: the param group's lr is the value itself
+            for o in (self.ox, self.oy):
+                for g in o.param_groups:
+                    g["lr"] = 1.0
+                self.schedulers.append(torch.optim.lr_scheduler.LambdaLR(o, schedule.lr))
         self.sampler = DistributedSampler(dataset, shuffle=True) if dist.is_initialized() else None
         self.loader = DataLoader(dataset, batch_size=batch, sampler=self.sampler, shuffle=False,
                                  pin_memory=device.type == "cuda")
@@ -80,6 +89,8 @@ class StockLoop:
                 torch.nn.utils.clip_grad_value_(m.parameters(), self.clip_grad_value)
         self.ox.step()
         self.oy.step()
+        for s in self.schedulers:
+            s.step()
         b = target.size(0)
         rx = lx.detach().cpu() * b
         ry = ly.detach().cpu() * b

@@ -21,6 +21,13 @@ struct DtpHyper {
   double lr, beta1, beta2, eps, weight_decay, momentum;
   float slope;        // LeakyReLU negative slope
   float grad_scale;   // applied to the summed gradient before the update (1/world for DDP averaging)
+  // learning-rate schedule: the step that follows t taken steps (the device step counter
+  // before it) uses lr_tab[min(t, lr_tab_len - 1)] in place of lr.  Device memory, float64
+  // (torch's param-group lr); null: lr.  The owner keeps it alive while launches or
+  // captured graphs can run.
+  const double* lr_tab;
+  int lr_tab_len;
+  int pad_;
 };
 
 struct DtpTrainArgs {
@@ -50,6 +57,9 @@ struct DtpTrainArgs {
   // Adam bias-correction scalars {lr / (1 - b1^t), sqrt(1 - b2^t)} of step t at [t], formed on
   // the host in f64 (torch's math); [len - 1] holds the saturated values (every later t).
   // Nullable: the kernel forms them itself.  Used with host_t0 >= 0 (the persistent engine).
+  // With a learning-rate schedule (hp.lr_tab) the table is required; its rows carry the step's
+  // rate: Adam {lr_t / (1 - b1^t), ...} (host_t0 >= 0 required), SGD {lr_t, 1} (either source
+  // of t0), with lr_t the rate after t - 1 taken steps.
   const float* adam_tab;  // [adam_tab_len][2]
   int adam_tab_len;
   int xbuf_bytes;  // MODE_XGMI_*: bytes of each rank's receive buffer (0: unchecked)

@@ -134,7 +134,7 @@ DTP_DEV void stage_bwd_body(const DtpStageArgs& a, const DtpOptArgs& o) {
         a.grad_params[p] = zg ? 0.f : gt;
       }
     } else {
-      const float lr = (float)o.hp.lr, mom = (float)o.hp.momentum, wd = (float)o.hp.weight_decay;
+      const float lr = (float)lr_of(o.hp, t), mom = (float)o.hp.momentum, wd = (float)o.hp.weight_decay;
       for (int p = tid; p < S::P; p += kBlock) {
         const float g = sum_partial_tiles<S>(&sm.stage[0][0], tile_pos<S>(p), 4);
         const float gt = a.accumulate ? a.grad_params[p] + g : g;

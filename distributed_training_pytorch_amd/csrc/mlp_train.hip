@@ -185,7 +185,13 @@ __global__ __launch_bounds__(kBlock) DTP_TRAIN_ATTR void mlp_train_kernel(DtpTra
   const int t0 = a.host_t0 >= 0 ? a.host_t0 : a.step[model];
   // the host's Adam-scalar table (persistent engine): the first kAdamTab entries are
   // loaded with the prologue's other global reads (one memory round trip for all)
-  const bool htab = kAdam && a.adam_tab && a.host_t0 >= 0;
+  // A learning-rate schedule (hp.lr_tab set) comes as a host table whose rows carry the
+  // step's rate -- Adam {lr_t / (1 - b1^t), sqrt(1 - b2^t)}, SGD {lr_t, 1} -- so the Adam
+  // instances are the unscheduled kernels to the instruction: a scheduled Adam launch gives
+  // host_t0 (dtp_mlp_train refuses it otherwise).  SGD reads its table with t0 from either
+  // source; without a schedule it reads hp.lr as before.
+  const bool ltab = kUpdate && !kAdam && a.adam_tab && a.hp.lr_tab;
+  const bool htab = (kAdam && a.adam_tab && a.host_t0 >= 0) || ltab;
   float2 tabv[kAdamTab / kBlock];
   if (htab) adam_tab_load<kAdamTab / kBlock>(a, t0, 0, tid, tabv);
   // 32-bit step bookkeeping, advanced incrementally (no 64-bit divisions per step)
@@ -312,7 +318,7 @@ __global__ __launch_bounds__(kBlock) DTP_TRAIN_ATTR void mlp_train_kernel(DtpTra
       sm.adam_tab[e] = make_float2((float)(a.hp.lr / bc1), (float)sqrt(bc2));
     }
   };
-  if (kAdam) fill_adam(0);
+  if (kAdam || ltab) fill_adam(0);
   stamp_launch(23);
   float* const stg_pack = &sm.stage[wave][0][0];
   __syncthreads();  // scattered weight blocks and the Adam table visible to every wave
@@ -443,6 +449,7 @@ __global__ __launch_bounds__(kBlock) DTP_TRAIN_ATTR void mlp_train_kernel(DtpTra
     // this step's Adam scalars: requested now, consumed after the reduction
     float2 adam_sc = make_float2(0.f, 1.f);
     if constexpr (kAdam) adam_sc = sm.adam_tab[it % kAdamTab];
+    else if (ltab) adam_sc = sm.adam_tab[it % kAdamTab];
     DTP_STAMP(4);
 
     float g[NPT];
@@ -510,7 +517,7 @@ __global__ __launch_bounds__(kBlock) DTP_TRAIN_ATTR void mlp_train_kernel(DtpTra
       AdamScalars as = adam_consts(a.hp);
       as.step_size = adam_sc.x;
       as.bc2_sqrt = adam_sc.y;
-      const float lr = (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
+      const float lr = ltab ? adam_sc.x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
       // branch-free over the thread's NPT slots (slots past P hold zeros and store
       // into sm.sink), so the compiler can interleave the slots' dependency chains
 #pragma unroll
@@ -535,7 +542,7 @@ __global__ __launch_bounds__(kBlock) DTP_TRAIN_ATTR void mlp_train_kernel(DtpTra
     __syncthreads();  // updated weights visible; reduction tiles consumed
     // the next kAdamTab steps' Adam scalars, once every kAdamTab steps at a step
     // boundary (every wave read this step's entry before the barrier above)
-    if (kAdam && (it + 1) % kAdamTab == 0 && it + 1 < a.n_steps) {
+    if ((kAdam || ltab) && (it + 1) % kAdamTab == 0 && it + 1 < a.n_steps) {
       fill_adam(it + 1);
       __syncthreads();
     }
@@ -812,7 +819,9 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     }
   }
   const int t0 = a.host_t0 >= 0 ? a.host_t0 : a.step[model];
-  const bool htab = kAdam && a.adam_tab && a.host_t0 >= 0;
+  // a schedule always comes as a host table, SGD's rows {lr_t, 1} (see mlp_train_kernel)
+  const bool ltab = !kAdam && a.adam_tab && a.hp.lr_tab;
+  const bool htab = (kAdam && a.adam_tab && a.host_t0 >= 0) || ltab;
   float2 tabv[kAdamTab / NTH];
   if (htab) adam_tab_load<kAdamTab / NTH, NTH>(a, t0, 0, tid, tabv);
   int epoch = t0 / smp.steps_per_epoch;
@@ -925,7 +934,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       sm.adam_tab[e] = make_float2((float)(a.hp.lr / bc1), (float)sqrt(bc2));
     }
   };
-  if (kAdam) fill_adam(0);
+  if (kAdam || ltab) fill_adam(0);
   stamp_launch(23);
   // per-lane LDS bases: the part's slice of the partitioned blocks, the sample's slot in a
   // staged operand (+ the part's first column), the MFMA reader's operands
@@ -1138,7 +1147,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       }
     }
     __syncthreads();
-    const float2 adam_sc = kAdam ? sm.adam_tab[it % kAdamTab] : make_float2(0.f, 1.f);
+    const float2 adam_sc = (kAdam || ltab) ? sm.adam_tab[it % kAdamTab] : make_float2(0.f, 1.f);
     DTP_STAMP(4);
     float g[NPT];
     float lsum = 0.f;
@@ -1265,7 +1274,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       AdamScalars as = adam_consts(a.hp);
       as.step_size = adam_sc.x;
       as.bc2_sqrt = adam_sc.y;
-      const float lr = (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
+      const float lr = ltab ? adam_sc.x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
 #pragma unroll
       for (int k = 0; k < NPT; ++k) {
         if constexpr (kAdam) adam_update(pw[k], mr[k], vr[k], g[k] * a.hp.grad_scale, as);
@@ -1298,12 +1307,12 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     DTP_STAMP(6);
     __syncthreads();
     if constexpr (kDiet && (DTP_GRP_DIET & 32)) {
-      if (kAdam && --refill == 0 && it + 1 < a.n_steps) {
+      if ((kAdam || ltab) && --refill == 0 && it + 1 < a.n_steps) {
         refill = kAdamTab;
         fill_adam(it + 1);
         __syncthreads();
       }
-    } else if (kAdam && (it + 1) % kAdamTab == 0 && it + 1 < a.n_steps) {
+    } else if ((kAdam || ltab) && (it + 1) % kAdamTab == 0 && it + 1 < a.n_steps) {
       fill_adam(it + 1);
       __syncthreads();
     }
@@ -1669,6 +1678,9 @@ int validate_train(const DtpTrainArgs* a, int mode) {
     return set_err(-1, "table sampler needs a power-of-two permutation ring");
   if (a->loss_log && a->loss_log_cap <= 0) return set_err(-1, "loss_log_cap must be positive");
   if (!a->params || !a->X || !a->Y || !a->step) return set_err(-1, "params, X, Y and step are required");
+  // the fused step reads a schedule's rates from the host-formed table (its rows carry them)
+  if (mode != DTP_MODE_GRAD && a->hp.lr_tab && (!a->adam_tab || a->adam_tab_len <= 0 || a->hp.lr_tab_len <= 0))
+    return set_err(-1, "a learning-rate schedule needs the host-formed per-step table (adam_tab)");
   if (mode == DTP_MODE_GRAD && !a->grad_out) return set_err(-1, "MODE_GRAD needs grad_out");
   if (mode != DTP_MODE_GRAD && !a->opt_m) return set_err(-1, "optimizer modes need opt_m");
   if ((mode == DTP_MODE_ADAM || mode == DTP_MODE_XGMI_ADAM) && !a->opt_v) return set_err(-1, "Adam needs opt_v");
@@ -1774,9 +1786,21 @@ int dtp_mlp_param_count(int in, int h, int nl, int out) {
   return p;
 }
 
+// The Adam instances read the host-formed table only with the host's step number (they are
+// the unscheduled kernels to the byte), so a scheduled Adam launch that would read its step
+// number on the device -- an eager launch without host_t0, a captured graph -- is refused
+// on every launch path instead of training at hp.lr.
+static int check_sched_t0(const DtpTrainArgs& a, int mode, int t0) {
+  if ((mode == DTP_MODE_ADAM || mode == DTP_MODE_XGMI_ADAM) && a.hp.lr_tab && t0 < 0)
+    return set_err(-1, "Adam under a learning-rate schedule reads the host-formed table: give the step number "
+                       "(host_t0 / t0 >= 0); it cannot be captured in a graph");
+  return 0;
+}
+
 int dtp_mlp_train(const DtpTrainArgs* a, int in, int h, int nl, int out, int mode, void* stream) {
   if (int rc = validate_train(a, mode)) return rc;
   if (mode == DTP_MODE_GRAD && a->n_steps != 1) return set_err(-4, "MODE_GRAD requires n_steps == 1");
+  if (int rc = check_sched_t0(*a, mode, a->host_t0)) return rc;
   LanePick lp;
   TrainLaunchFn fn = resolve_train(*a, in, h, nl, out, mode, &lp);
   if (!fn) return set_err(-2, "mlp shape / mode not instantiated for the fused train kernel");
@@ -1875,6 +1899,7 @@ int dtp_train_engine_run(void* h, int n_steps, int t0, void* stream) {
   if (!e) return set_err(-1, "null engine");
   if (n_steps <= 0) return set_err(-1, "n_steps must be positive");
   if (e->mode == DTP_MODE_GRAD && n_steps != 1) return set_err(-4, "MODE_GRAD requires n_steps == 1");
+  if (int rc = check_sched_t0(e->a, e->mode, t0)) return rc;  // (dtp_graph_capture_engine runs with t0 = -1)
   e->a.n_steps = n_steps;
   e->a.host_t0 = t0;
   e->fn(e->a, (hipStream_t)stream);

@@ -248,7 +248,7 @@ DTP_DEV void flat_optimizer_body(const DtpOptArgs& a) {
       v[i] = vi;
     }
   } else {
-    const float lr = (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
+    const float lr = (float)lr_of(a.hp, t), mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.P; i += gridDim.x * kBlock) {
       float w = p[i], bi = m[i];
       const float gv = g[i];
@@ -323,6 +323,7 @@ extern "C" int dtp_clip_grad_norm(float* grad, int n_models, int P, float max_no
 extern "C" int dtp_flat_optimizer(const DtpOptArgs* a, void* stream) {
   if (!a || a->P <= 0 || a->n_models <= 0) return -1;
   if (a->kind != DTP_MODE_ADAM && a->kind != DTP_MODE_SGD) return -2;
+  if (a->hp.lr_tab && a->hp.lr_tab_len <= 0) return set_err(-6, "flat_optimizer: a learning-rate table needs at least one entry");
   hipStream_t st = (hipStream_t)stream;
   // small models (the toy's 371 parameters): one block per model loops over its
   // parameters and advances the step counter itself -- no follow-up launch

@@ -15,11 +15,18 @@ struct AdamScalars {
   float step_size, bc2_sqrt, one_m_b1, b2, one_m_b2, eps, wd;
 };
 
+// the learning rate of the step taken after t steps (t = the step counter before the step,
+// 0-based): the schedule's table entry, its last one for ever past its end; no table: hp.lr
+DTP_DEV double lr_of(const DtpHyper& hp, long long t) {
+  if (!hp.lr_tab || hp.lr_tab_len <= 0) return hp.lr;  // (an empty table is never read)
+  return hp.lr_tab[t < hp.lr_tab_len ? t : hp.lr_tab_len - 1];
+}
+
 DTP_DEV AdamScalars adam_scalars(const DtpHyper& hp, long long t1) {
   AdamScalars s;
   const double bc1 = 1.0 - pow_int(hp.beta1, (uint64_t)t1);
   const double bc2 = 1.0 - pow_int(hp.beta2, (uint64_t)t1);
-  s.step_size = (float)(hp.lr / bc1);
+  s.step_size = (float)(lr_of(hp, t1 - 1) / bc1);
   s.bc2_sqrt = (float)sqrt(bc2);
   s.one_m_b1 = (float)(1.0 - hp.beta1);
   s.b2 = (float)hp.beta2;

@@ -195,6 +195,8 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
   constexpr int TS = C::TS, H = S::H, PL = C::PL;
   Sm& sm = *reinterpret_cast<Sm*>(smem);
   const bool adam = a.optim == DTP_MODE_ADAM;
+  // the per-step scalars come from the LDS table: Adam always, SGD under a learning-rate schedule
+  const bool tab = adam || a.hp.lr_tab;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int part = lane & (C::L - 1), ws = lane / C::L;
   const SamplerCfg smp = a.smp;
@@ -287,11 +289,16 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
     const int n = min(kSLAdamTab, a.n_steps - base);
     for (int e = tid; e < n; e += NTH) {
       const uint64_t t1 = (uint64_t)t0 + (uint64_t)base + (uint64_t)e + 1u;
+      const double lr_t = lr_of(a.hp, (long long)t1 - 1);  // the rate after t1 - 1 taken steps
+      if (!adam) {  // SGD with a schedule: rows {lr_t, 1}
+        sm.adam_tab[e] = make_float2((float)lr_t, 1.f);
+        continue;
+      }
       const double bc1 = 1.0 - pow_int(a.hp.beta1, t1), bc2 = 1.0 - pow_int(a.hp.beta2, t1);
-      sm.adam_tab[e] = make_float2((float)(a.hp.lr / bc1), (float)sqrt(bc2));
+      sm.adam_tab[e] = make_float2((float)(lr_t / bc1), (float)sqrt(bc2));
     }
   };
-  if (adam) fill_adam(0);
+  if (tab) fill_adam(0);
   __syncthreads();  // weights scattered, Adam table formed
   if constexpr (FIRST || LAST) gather(fidx0, nx, ny);
 
@@ -591,7 +598,7 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
 #pragma unroll
       for (int k = 0; k < NPT; ++k) adam_update(pw[k], mr[k], vr[k], g[k] * gs, as);
     } else {
-      const float lr = (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
+      const float lr = a.hp.lr_tab ? sm.adam_tab[it % kSLAdamTab].x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
 #pragma unroll
       for (int k = 0; k < NPT; ++k) sgd_update(pw[k], mr[k], g[k] * gs, lr, mom, wd, t == 0);
     }
@@ -606,7 +613,7 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
       if (tid == 0 && lead && a.loss_log) a.loss_log[t % a.loss_log_cap] = use_dp ? gloss * gs : gloss;
     }
     __syncthreads();  // new weights visible; parked tiles consumed before the next park
-    if (adam && (it + 1) % kSLAdamTab == 0 && it + 1 < a.n_steps) {
+    if (tab && (it + 1) % kSLAdamTab == 0 && it + 1 < a.n_steps) {
       fill_adam(it + 1);
       __syncthreads();
     }

@@ -138,6 +138,8 @@ DTP_DEV void split_stage_body_v1(const DtpSplitStageArgs& a, unsigned char* smem
   static_assert(sizeof(SplitSmem<S>) <= kSplitSmemBytes, "stage LDS exceeds the shared block");
   SplitSmem<S>& sm = *reinterpret_cast<SplitSmem<S>*>(smem);
   const bool adam = a.optim == DTP_MODE_ADAM;
+  // the per-step scalars come from the LDS table: Adam always, SGD under a learning-rate schedule
+  const bool tab = adam || a.hp.lr_tab;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const SamplerCfg smp = a.smp;
   const float slope = a.hp.slope;
@@ -223,11 +225,16 @@ DTP_DEV void split_stage_body_v1(const DtpSplitStageArgs& a, unsigned char* smem
     const int n = min(kSplitAdamTab, a.n_steps - base);
     for (int e = tid; e < n; e += kBlock) {
       const uint64_t t1 = (uint64_t)t0 + (uint64_t)base + (uint64_t)e + 1u;
+      const double lr_t = lr_of(a.hp, (long long)t1 - 1);  // the rate after t1 - 1 taken steps
+      if (!adam) {  // SGD with a schedule: rows {lr_t, 1}
+        sm.adam_tab[e] = make_float2((float)lr_t, 1.f);
+        continue;
+      }
       const double bc1 = 1.0 - pow_int(a.hp.beta1, t1), bc2 = 1.0 - pow_int(a.hp.beta2, t1);
-      sm.adam_tab[e] = make_float2((float)(a.hp.lr / bc1), (float)sqrt(bc2));
+      sm.adam_tab[e] = make_float2((float)(lr_t / bc1), (float)sqrt(bc2));
     }
   };
-  if (adam) fill_adam(0);
+  if (tab) fill_adam(0);
   __syncthreads();  // pads zeroed before the owners scatter
 #pragma unroll
   for (int k = 0; k < NPT; ++k) {
@@ -328,7 +335,7 @@ DTP_DEV void split_stage_body_v1(const DtpSplitStageArgs& a, unsigned char* smem
       for (int k = 0; k < NPT; ++k)
         if (lp[k] >= 0) adam_update(pw[k], mr[k], vr[k], g[k] * gs, as);
     } else {
-      const float lr = (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
+      const float lr = a.hp.lr_tab ? sm.adam_tab[it % kSplitAdamTab].x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
 #pragma unroll
       for (int k = 0; k < NPT; ++k)
         if (lp[k] >= 0) sgd_update(pw[k], mr[k], g[k] * gs, lr, mom, wd, t == 0);
@@ -343,7 +350,7 @@ DTP_DEV void split_stage_body_v1(const DtpSplitStageArgs& a, unsigned char* smem
       if (tid == owner && a.loss_log) a.loss_log[t % a.loss_log_cap] = use_dp ? gloss * gs : loss;
     }
     __syncthreads();  // new weights visible; reduction tiles consumed before the next staging writes
-    if (adam && (it + 1) % kSplitAdamTab == 0 && it + 1 < a.n_steps) {
+    if (tab && (it + 1) % kSplitAdamTab == 0 && it + 1 < a.n_steps) {
       fill_adam(it + 1);  // every thread read this step's entry before the barrier above
       __syncthreads();
     }
@@ -391,6 +398,8 @@ DTP_DEV void split_stage_body_pipe(const DtpSplitStageArgs& a, unsigned char* sm
   static_assert(sizeof(SplitPipeSmem<S>) <= kSplitSmemBytes, "stage LDS exceeds the shared block");
   SplitPipeSmem<S>& sm = *reinterpret_cast<SplitPipeSmem<S>*>(smem);
   const bool adam = a.optim == DTP_MODE_ADAM;
+  // the per-step scalars come from the LDS table: Adam always, SGD under a learning-rate schedule
+  const bool tab = adam || a.hp.lr_tab;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const SamplerCfg smp = a.smp;
   const float slope = a.hp.slope;
@@ -483,11 +492,16 @@ DTP_DEV void split_stage_body_pipe(const DtpSplitStageArgs& a, unsigned char* sm
     const int n = min(kSplitAdamTab, a.n_steps - base);
     for (int e = tid; e < n; e += kBlock) {
       const uint64_t t1 = (uint64_t)t0 + (uint64_t)base + (uint64_t)e + 1u;
+      const double lr_t = lr_of(a.hp, (long long)t1 - 1);  // the rate after t1 - 1 taken steps
+      if (!adam) {  // SGD with a schedule: rows {lr_t, 1}
+        sm.adam_tab[e] = make_float2((float)lr_t, 1.f);
+        continue;
+      }
       const double bc1 = 1.0 - pow_int(a.hp.beta1, t1), bc2 = 1.0 - pow_int(a.hp.beta2, t1);
-      sm.adam_tab[e] = make_float2((float)(a.hp.lr / bc1), (float)sqrt(bc2));
+      sm.adam_tab[e] = make_float2((float)(lr_t / bc1), (float)sqrt(bc2));
     }
   };
-  if (adam) fill_adam(0);
+  if (tab) fill_adam(0);
   auto scatter = [&]() {
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
@@ -653,7 +667,7 @@ DTP_DEV void split_stage_body_pipe(const DtpSplitStageArgs& a, unsigned char* sm
 #pragma unroll
       for (int k = 0; k < NPT; ++k) adam_update(pw[k], mr[k], vr[k], g[k] * gs, as);
     } else {
-      const float lr = (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
+      const float lr = a.hp.lr_tab ? sm.adam_tab[it % kSplitAdamTab].x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
 #pragma unroll
       for (int k = 0; k < NPT; ++k) sgd_update(pw[k], mr[k], g[k] * gs, lr, mom, wd, t == 0);
     }
@@ -665,7 +679,7 @@ DTP_DEV void split_stage_body_pipe(const DtpSplitStageArgs& a, unsigned char* sm
     SPLIT_STAMP(8);
     __syncthreads();  // new weights visible; reduction tiles consumed before the next staging writes
     SPLIT_STAMP(9);
-    if (adam && (it + 1) % kSplitAdamTab == 0 && it + 1 < a.n_steps) {
+    if (tab && (it + 1) % kSplitAdamTab == 0 && it + 1 < a.n_steps) {
       fill_adam(it + 1);
       __syncthreads();
     }

@@ -123,12 +123,21 @@ class FusedTrainer:
             # Adam's per-step scalars, formed once on the host (f64, the kernels' own
             # arithmetic): a persistent launch loads them with its other prologue reads
             self._adam_tab = None
-            if self.optim.name == "adam":
+            if self.optim.name == "adam" or self.optim.schedule is not None:
                 from ..ops.optim import adam_bias_table
 
+                # with a learning-rate schedule the rows carry every step's rate (SGD: {lr_t, 1})
+                # and every launch mode reads them: the step kernels' loop and their own fill
+                # stay those of the fixed rate
                 tab = adam_bias_table(self.optim)
                 if tab is not None:
                     self._adam_tab = torch.from_numpy(tab).to(dev)
+                elif self.optim.schedule is not None and self.comm not in ("rccl", "host"):
+                    # (rccl / host: the gradient kernel plus the flat optimizer, which looks the
+                    # rate up in the schedule's own device table -- no cap there)
+                    raise NotImplementedError("the fused step reads a schedule from the host-formed per-step "
+                                              "table: the schedule (or Adam's bias-correction horizon, betas ~ 1) "
+                                              "is longer than its 4M rows")
             if geom.mode == SAMPLER_DIST_SHUFFLE:
                 if self.cfg.sampler not in ("torch", "device"):
                     raise ValueError(f"sampler {self.cfg.sampler!r}: torch or device")
@@ -297,7 +306,9 @@ class FusedTrainer:
             self.t = saved_t
 
     def _hyper(self, grad_scale: float) -> nat.Hyper:
-        return self.optim.hyper(self.spec.slope, grad_scale)
+        # a schedule's device table is cached by self.optim.schedule, which this engine holds
+        # for as long as its executor and captured graphs live
+        return self.optim.hyper(self.spec.slope, grad_scale, self.device)
 
     def _train_args(self, n_steps: int, mode: int, idx: torch.Tensor | None, batch_override: int | None = None):
         g = self.geom
@@ -372,7 +383,12 @@ class FusedTrainer:
                 k = min(remaining, self.cfg.steps_per_launch)
                 self._ensure_epochs(k)
                 self._run_engine(k)
-            elif self.cfg.launch == "graph":
+            elif self.cfg.launch == "graph" and not (self.optim.schedule is not None and self.optim.name == "adam"):
+                # (scheduled Adam: its table is indexed by the host's step number, which a
+                # captured launch cannot carry -- the library refuses the capture -- so those
+                # steps run as the one-step launches below.  Letting the Adam instances index
+                # the table by the device counter cost the default step 2.2 - 2.4 %:
+                # profiles/lr_schedule/README.md)
                 G = self.cfg.steps_per_launch
                 if remaining >= G:
                     self._ensure_epochs(G)

@@ -106,7 +106,33 @@ def _fused_supported(config) -> bool:
 
 def _optim(config) -> OptimConfig:
     return OptimConfig(config.optimizer, config.lr, momentum=config.momentum, weight_decay=config.weight_decay,
-                       max_grad_norm=_clip_norm(config), clip_grad_value=_clip_value(config))
+                       max_grad_norm=_clip_norm(config), clip_grad_value=_clip_value(config),
+                       schedule=lr_schedule(config))
+
+
+def lr_schedule(config):
+    """The ``LrSchedule`` of --lr_schedule / --warmup_iters / --lr_decay_iters / --lr_min_ratio /
+    --lr_step_size / --lr_gamma; None with the defaults (the fixed --lr, no table at all).
+    A function of the step number alone, so --resume with the same flags continues the curve."""
+    from ..ops.schedule import LrSchedule
+
+    kind = getattr(config, "lr_schedule", "constant") or "constant"
+    warm = int(getattr(config, "warmup_iters", 0) or 0)
+    if kind == "constant" and warm <= 0:
+        return None
+    decay = getattr(config, "lr_decay_iters", None)
+    return LrSchedule.make(kind, config.lr, warmup_iters=warm,
+                           decay_iters=config.iters if decay is None else decay,
+                           min_ratio=getattr(config, "lr_min_ratio", 0.0),
+                           step_size=getattr(config, "lr_step_size", None),
+                           gamma=getattr(config, "lr_gamma", 0.1), total=max(int(config.iters), 1))
+
+
+def _lr_summary(config, iters: int) -> dict:
+    """``lr_schedule`` and ``lr_last`` (the rate of the last step taken) of the run summary."""
+    sched = lr_schedule(config)
+    last = float(config.lr) if sched is None or iters <= 0 else sched.lr(iters - 1)
+    return {"lr_schedule": getattr(config, "lr_schedule", "constant"), "lr_last": last}
 
 
 def _clip_norm(config) -> float:
@@ -224,6 +250,7 @@ def train(config, env, device, rank, world, group: str = "base-demo") -> dict:
     wall = time.perf_counter() - t_start
     logger.finish()
     summary["wall_s"] = wall
+    summary.update(_lr_summary(config, int(summary.get("iters", 0))))
     rank_print(rank, "Finished")
     return summary
 
@@ -572,7 +599,8 @@ def _train_stock(config, device, rank, world, logger, faults) -> dict:
 
     ds = _dataset(config, rank)
     loop = StockLoop(ds, device, batch=config.batch_size, seed=config.seed,
-                     clip_grad_norm=_clip_norm(config), clip_grad_value=_clip_value(config))
+                     clip_grad_norm=_clip_norm(config), clip_grad_value=_clip_value(config),
+                     schedule=lr_schedule(config))
     pbar = _progress(rank, config.iters, config)
     timer = PhaseTimer(device)
     val = _Validation(config, ds, rank, world, device, logger)

@@ -13,6 +13,7 @@ from dataclasses import dataclass
 import torch
 
 from .. import _native as nat
+from .schedule import LrSchedule, lr_at
 
 
 @dataclass
@@ -26,6 +27,8 @@ class OptimConfig:
     # gradient clipping, per row (one model = one optimizer); 0 = off, at most one of them:
     max_grad_norm: float = 0.0    # > 0: torch.nn.utils.clip_grad_norm_(row, max_grad_norm)
     clip_grad_value: float = 0.0  # > 0: torch.nn.utils.clip_grad_value_(row, clip_grad_value)
+    # the rate of every step (ops.schedule); None: ``lr`` at every step
+    schedule: LrSchedule | None = None
 
     def __post_init__(self):
         if self.max_grad_norm > 0 and self.clip_grad_value > 0:
@@ -43,9 +46,22 @@ class OptimConfig:
             return nat.MODE_SGD
         raise ValueError(f"unknown optimizer {self.name!r}")
 
-    def hyper(self, slope: float = 0.01, grad_scale: float = 1.0) -> nat.Hyper:
-        return nat.Hyper(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.momentum,
-                         slope, grad_scale)
+    def hyper(self, slope: float = 0.01, grad_scale: float = 1.0, device=None) -> nat.Hyper:
+        """The kernels' hyperparameters.  With a schedule, ``device`` is where the launch
+        runs: the table lives there (cached by the schedule, which this config keeps alive)."""
+        hp = nat.Hyper(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.momentum,
+                       slope, grad_scale)
+        if self.schedule is not None:
+            if device is None:
+                raise ValueError("OptimConfig.hyper: a schedule needs the device of the launch")
+            tab = self.schedule.device_table(device)
+            hp.lr_tab = tab.data_ptr()
+            hp.lr_tab_len = tab.numel()
+        return hp
+
+    def lr_at(self, t: int) -> float:
+        """The rate of the step taken after ``t`` steps."""
+        return lr_at(self, t)
 
     def torch_optimizer(self, params):
         if self.name == "adam":
@@ -56,7 +72,8 @@ class OptimConfig:
 
 def adam_update_ref(p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.Tensor, t1: int,
                     cfg: OptimConfig) -> None:
-    """In-place Adam step number t1 (1-based) with torch's operation order (fp32)."""
+    """In-place Adam step number t1 (1-based) with torch's operation order (fp32); the rate
+    is that of the step taken after t1 - 1 steps."""
     b1, b2 = cfg.betas
     if cfg.weight_decay:
         g = g + cfg.weight_decay * p
@@ -65,7 +82,7 @@ def adam_update_ref(p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.
     bc1 = 1 - b1 ** t1
     bc2 = 1 - b2 ** t1
     denom = (v.sqrt() / math.sqrt(bc2)).add_(cfg.eps)
-    p.addcdiv_(m, denom, value=-(cfg.lr / bc1))
+    p.addcdiv_(m, denom, value=-(cfg.lr_at(t1 - 1) / bc1))
 
 
 def adam_bias_table(cfg: "OptimConfig", max_len: int = 1 << 22):
@@ -74,9 +91,20 @@ def adam_bias_table(cfg: "OptimConfig", max_len: int = 1 << 22):
     (``pow_int``: repeated squaring, ``csrc/dtp_common.h``), so a launch reading this
     table is bitwise the launch that forms the scalars itself.  The table ends at the
     first t where both corrections are exactly 1.0 in float64; every later step uses
-    that last row.  None if that takes more than ``max_len`` steps (beta ~ 1)."""
+    that last row.  With a schedule the rows run to the later of that and the schedule's
+    end (row t is the step taken after t - 1 steps).  None if that takes more than
+    ``max_len`` steps (beta ~ 1, or a longer schedule): the kernel's own fill takes over."""
     import numpy as np
 
+    if cfg.name == "sgd":
+        # SGD under a schedule takes its per-step rate from the same table: rows {lr_t, 1}
+        # (row t = the step taken after t - 1 steps); no schedule: no table, hp.lr
+        if cfg.schedule is None or len(cfg.schedule) + 1 > max_len:
+            return None
+        vals = np.asarray(cfg.schedule.values, dtype=np.float64)
+        t = np.arange(len(vals) + 1, dtype=np.int64)
+        return np.stack([vals[np.clip(t - 1, 0, len(vals) - 1)].astype(np.float32),
+                         np.ones(len(t), dtype=np.float32)], axis=1)
     b1, b2 = float(cfg.betas[0]), float(cfg.betas[1])
 
     def pow_int(b: float, t: "np.ndarray") -> "np.ndarray":
@@ -109,13 +137,28 @@ def adam_bias_table(cfg: "OptimConfig", max_len: int = 1 << 22):
     if not done.size:
         return None
     T = int(done[0])
+    if cfg.schedule is None:
+        with np.errstate(divide="ignore"):
+            tab = np.stack([(float(cfg.lr) / bc1[:T + 1]).astype(np.float32),
+                            np.sqrt(bc2[:T + 1]).astype(np.float32)], axis=1)
+        return tab
+    # row t1 = step number t1 = the step taken after t1 - 1 steps: rate values[min(t1 - 1, len - 1)]
+    vals = np.asarray(cfg.schedule.values, dtype=np.float64)
+    T = max(T, len(vals))
+    if T + 1 > max_len:
+        return None
+    t = np.arange(T + 1, dtype=np.int64)
+    bc1 = 1.0 - pow_int(b1, t)
+    bc2 = 1.0 - pow_int(b2, t)
+    lr_t = vals[np.clip(t - 1, 0, len(vals) - 1)]
     with np.errstate(divide="ignore"):
-        tab = np.stack([(float(cfg.lr) / bc1[:T + 1]).astype(np.float32),
-                        np.sqrt(bc2[:T + 1]).astype(np.float32)], axis=1)
+        tab = np.stack([(lr_t / bc1).astype(np.float32), np.sqrt(bc2).astype(np.float32)], axis=1)
     return tab
 
 
-def sgd_update_ref(p: torch.Tensor, buf: torch.Tensor, g: torch.Tensor, first: bool, cfg: OptimConfig) -> None:
+def sgd_update_ref(p: torch.Tensor, buf: torch.Tensor, g: torch.Tensor, first: bool, cfg: OptimConfig,
+                   lr: float | None = None) -> None:
+    """``lr``: this step's rate under a schedule (``cfg.lr_at(t)``); None: ``cfg.lr``."""
     if cfg.weight_decay:
         g = g + cfg.weight_decay * p
     if cfg.momentum:
@@ -124,7 +167,7 @@ def sgd_update_ref(p: torch.Tensor, buf: torch.Tensor, g: torch.Tensor, first: b
         else:
             buf.mul_(cfg.momentum).add_(g)
         g = buf
-    p.add_(g, alpha=-cfg.lr)
+    p.add_(g, alpha=-(cfg.lr if lr is None else lr))
 
 
 def grad_norm_ws(P: int, n_models: int, device) -> torch.Tensor | None:
@@ -237,7 +280,7 @@ def flat_optimizer_step(params, m, v, step, grad, cfg: OptimConfig, grad_scale: 
                 norm_ws = grad_norm_ws(P, n_models, params.device)
         a = nat.OptArgs(nat.ptr(params), nat.ptr(m), nat.ptr(v), nat.ptr(step), nat.ptr(grad),
                         nat.ptr(loss_log), 0 if loss_log is None else loss_log.shape[0], n_models, P, cfg.kind,
-                        loss_scale, 1 if zero_grad else 0, cfg.hyper(slope, grad_scale), nat.ptr(shadow),
+                        loss_scale, 1 if zero_grad else 0, cfg.hyper(slope, grad_scale, params.device), nat.ptr(shadow),
                         0 if shadow is None else shadow.stride(0), max(cfg.max_grad_norm, 0.0),
                         max(cfg.clip_grad_value, 0.0), nat.ptr(norm_ws) if by_norm else None,
                         nat.ptr(norm_out) if by_norm else None)
@@ -268,7 +311,7 @@ def flat_optimizer_step(params, m, v, step, grad, cfg: OptimConfig, grad_scale: 
         if cfg.name == "adam":
             adam_update_ref(params[i], m[i], v[i], g[i], t + 1, cfg)
         else:
-            sgd_update_ref(params[i], m[i], g[i], t == 0, cfg)
+            sgd_update_ref(params[i], m[i], g[i], t == 0, cfg, cfg.lr_at(t))
         if loss_log is not None:
             loss_log[t % loss_log.shape[0], i] = grad[n_models * P + i] * loss_scale
         step[i] = t + 1
@@ -307,6 +350,9 @@ class FlatOptimizer:
         # clipping by norm: the result and the scratch are made here, never during a capture
         self.grad_norm = torch.zeros(n, dtype=torch.float32, device=self.params.device)
         self._norm_ws = grad_norm_ws(P, n, self.params.device) if self.cfg.max_grad_norm > 0 else None
+        # likewise a schedule's device table (cached by the schedule; hyper() finds it there)
+        if self.cfg.schedule is not None:
+            self.cfg.schedule.device_table(self.params.device)
 
     @torch.no_grad()
     def step(self, zero_grad: bool = False, fused=None) -> bool:

@@ -483,7 +483,9 @@ class FusedLayerSplit:
                 a.smp = geom.to_native()
                 if dev in self.rings and (s == 0 or s == K - 1):
                     self.rings[dev].native(a.smp)
-                a.hp = self.optim.hyper(spec.slope, 1.0 / self.world)
+                # a schedule's table on this stage's device, held by self.optim.schedule for
+                # as long as this object launches
+                a.hp = self.optim.hyper(spec.slope, 1.0 / self.world, dev)
                 a.grp_buf = nat.ptr(self._grp[s]) if self._grp[s] is not None else None
                 L.shape_id[j] = lib.dtp_split_shape_id(ss.in_features, ss.hidden, ss.n_layers, ss.out_features,
                                                        int(ss.final_act), int(s == 0))

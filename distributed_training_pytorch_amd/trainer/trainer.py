@@ -21,6 +21,7 @@ MI355X-first: a dataset exposing device tensors (``ToyData``) is gathered on the
 from __future__ import annotations
 
 import contextlib
+import copy
 import dataclasses
 import ctypes
 import csv
@@ -28,6 +29,7 @@ import datetime
 import math
 import os
 import time
+import warnings
 from pathlib import Path
 
 import torch
@@ -377,6 +379,9 @@ class Trainer:
         # run a plain torch Adam/SGD over a flat-buffer span as ONE flat-optimizer kernel (GPU)
         self.native_optimizers = native_optimizers
         self._flat_opts: list = []
+        # configure_optimizers' schedulers: {"scheduler", "interval", "frequency", "opt"} each
+        self._sched_recs: list = []
+        self.lr_tables: list = []  # per optimizer: the tabulated rates the kernels read, or None
         self._opt_zeroes = False  # the flat optimizers zero the gradient they consume (fit)
         # the backward's last stage kernel fused with the flat optimizer step (one rank);
         # DTP_TRAINER_FUSE_OPT=0 launches them separately (A/B)
@@ -457,9 +462,8 @@ class Trainer:
             torch.manual_seed(self.seed)
         model.trainer = self
         model.to(self.device)
-        opts = model.configure_optimizers()
-        if not isinstance(opts, (list, tuple)):
-            opts = [opts]
+        opts, self._sched_recs = _parse_optimizers(model.configure_optimizers())
+        self.lr_tables = [None] * len(opts)
         resume = self._resolve_ckpt(ckpt_path)
         if resume is not None:
             self._restore(model, opts, resume)
@@ -498,6 +502,7 @@ class Trainer:
             vloader = self._val_loader(val_dl)
             logger.allow_new_columns()
         spe = len(loader) if hasattr(loader, "__len__") else None
+        self._table_flat_opts(opts, spe)
         pbar = None
         if self.enable_progress_bar and self.global_rank == 0:
             try:
@@ -566,6 +571,11 @@ class Trainer:
                         self._optimizer_steps(model, ddp, opts, batch, batch_idx)
                         owner = None
                     self.global_step += 1  # PL 1.5: once per batch, whatever the optimizer count
+                    # the schedulers, before any hook, log or checkpoint can observe them
+                    for fo in self._flat_opts:
+                        if fo is not None:
+                            fo.host_t += 1
+                    self._advance_schedulers(self.global_step, spe)
                     if self.global_step == steady_from:
                         if self.device.type == "cuda":
                             torch.cuda.synchronize(self.device)
@@ -587,6 +597,8 @@ class Trainer:
                 else:
                     self.current_epoch += 1
                     self._batch_in_epoch = 0
+                    if spe is None:  # an unsized loader: the epoch's end is known only here
+                        self._advance_schedulers(self.current_epoch, None, epoch_end=True)
                 self._skip_batches = 0
                 if self.max_epochs is not None and self.current_epoch >= self.max_epochs:
                     done = True
@@ -674,8 +686,32 @@ class Trainer:
         ds = getattr(dl, "dataset", None)
         if not hasattr(ds, "device_tensors"):
             return no("the dataset has no device_tensors()")
+        optim = cfgs[0]
+        if self._sched_recs:
+            # the engine reads ONE table by its step counter: every optimizer's scheduler must
+            # tabulate (nothing but lr moves) and to the same values
+            distributed = self.world_size > 1
+            spe = SamplerGeometry(n=len(ds), world=self.world_size, rank=self.global_rank,
+                                  batch=int(getattr(dl, "batch_size", None) or 1), shuffle=distributed,
+                                  distributed=distributed, seed=0).steps_per_epoch
+            tabs = [self._tabulate(opts, i, self.global_step, spe) for i in range(len(opts))]
+            why = None
+            if any(t is None for i, t in enumerate(tabs) if any(r["opt"] == i for r in self._sched_recs)):
+                why = "a learning-rate scheduler cannot be tabulated (it moves more than lr, or has no planned length)"
+            elif any(t != tabs[0] for t in tabs):
+                why = "the optimizers' learning-rate tables differ (the fused engine has one OptimConfig)"
+            if why is not None:
+                self.fused_refused = why
+                if self.global_rank == 0 and self.engine != "fused":
+                    rank_print(0, f"Trainer: not using the fused engine ({why}); per-batch module path")
+                return no(why)
+            if tabs[0] is not None:
+                from ..ops.schedule import LrSchedule
+
+                optim = dataclasses.replace(optim, schedule=LrSchedule.from_values(tabs[0]))
+                self.lr_tables = list(tabs)
         prec = "fp32" if self.autocast_dtype is None else "bf16"
-        return {"models": models, "names": names, "loss": loss, "optim": cfgs[0], "dataset": ds,
+        return {"models": models, "names": names, "loss": loss, "optim": optim, "dataset": ds,
                 "val_names": list(fs.get("val_metrics") or []),
                 "batch": int(getattr(dl, "batch_size", None) or 1), "precision": prec, "spec": models[0].spec}
 
@@ -798,6 +834,11 @@ class Trainer:
                 s0 = self.global_step
                 tr.train(n)
                 self.global_step += n
+                # the real schedulers, to the count the engine's table has reached, before any
+                # hook, log or checkpoint can observe them
+                if self._sched_recs:
+                    for g in range(s0 + 1, self.global_step + 1):
+                        self._advance_schedulers(g, spe)
                 handle = tr.losses_async(s0, self.global_step)
                 if pending is not None:
                     drain(pending)
@@ -1059,7 +1100,8 @@ class Trainer:
             torch.save({"state_dict": {k: v.detach().cpu() for k, v in model.state_dict().items()},
                         "global_step": self.global_step, "epoch": self.current_epoch,
                         "batch_in_epoch": self._batch_in_epoch,
-                        "optimizer_states": [_cpu_state(o.state_dict()) for o in opts]}, tmp)
+                        "optimizer_states": [_cpu_state(o.state_dict()) for o in opts],
+                        "lr_schedulers": [_cpu_state(r["scheduler"].state_dict()) for r in self._sched_recs]}, tmp)
             os.replace(tmp, path)
             self.checkpoint_path = str(path)
         if dist.is_initialized():
@@ -1079,12 +1121,72 @@ class Trainer:
         model.load_state_dict(ck["state_dict"])
         for o, st in zip(opts, ck["optimizer_states"]):
             o.load_state_dict(st)
+        for r, st in zip(self._sched_recs, ck.get("lr_schedulers", [])):
+            r["scheduler"].load_state_dict(st)
         self.global_step = int(ck["global_step"])
         self.current_epoch = int(ck["epoch"])
         self._skip_batches = self._batch_in_epoch = int(ck.get("batch_in_epoch", 0))
         self.resumed_from = str(path)
         if self.global_rank == 0:
             rank_print(0, f"resumed from {path} at global_step {self.global_step}")
+
+    # ------------------------------------------------------------------ lr schedulers
+    @property
+    def lr_schedulers(self) -> list:
+        return [r["scheduler"] for r in self._sched_recs]
+
+    def _advance_schedulers(self, done: int, spe, epoch_end: bool = False) -> None:
+        """The schedulers due after batch number ``done`` (= global_step once it ran): a
+        step-interval one every ``frequency`` batches, after its own optimizer's step; an
+        epoch-interval one at the end of every ``frequency``-th epoch (``done`` a multiple
+        of the epoch's ``spe`` batches; ``epoch_end``: ``done`` counts epochs instead)."""
+        for r in self._sched_recs:
+            if _sched_due(r, done, spe, epoch_end):
+                if getattr(r["scheduler"], "_step_count", 2) <= 1:
+                    # torch warns once, at a scheduler's first step, when its optimizer's own
+                    # step() has not run: where the flat kernel or the fused engine steps, it never does
+                    with warnings.catch_warnings():
+                        warnings.filterwarnings("ignore", message="Detected call of `lr_scheduler.step")
+                        r["scheduler"].step()
+                else:
+                    r["scheduler"].step()
+
+    def _planned_steps(self, spe) -> int | None:
+        limits = [self.max_steps] if self.max_steps >= 0 else []
+        if self.max_epochs is not None and spe is not None:
+            limits.append(self.max_epochs * spe)
+        return min(limits) if limits else None
+
+    def _tabulate(self, opts, i: int, t0: int, spe):
+        """Optimizer i's rate of every planned step as a tuple indexed by its step count
+        (``t0`` steps taken so far; the entries below t0 are never read), from stepping a deep
+        copy of its schedulers as the fit will step the real ones.  None: no scheduler, no
+        planned length, or something other than ``lr`` moves in the param group."""
+        recs = [r for r in self._sched_recs if r["opt"] == i]
+        total = self._planned_steps(spe)
+        if not recs or total is None or total - self.global_step > _MAX_LR_TABLE or \
+                (spe is None and any(r["interval"] == "epoch" for r in recs)):
+            return None
+        return _tabulate_lr(opts[i], recs, t0, self.global_step, total, spe)
+
+    def _table_flat_opts(self, opts, spe) -> None:
+        """Module path: every flat-kernel optimizer whose schedulers tabulate reads its rate
+        from a device table by its own step counter -- graph replays included, with no
+        recapture; the others keep the per-batch ``refresh()`` of their param group."""
+        if not self._sched_recs:
+            return
+        for i, fo in enumerate(self._flat_opts):
+            if fo is None:
+                continue
+            if fo.cfg.name == "sgd" and self.global_step:
+                # torch's SGD keeps no step count: the restored counter only says "not the
+                # first step"; the table is indexed by the steps taken, one per batch
+                fo.flat.step_ctr.fill_(self.global_step)
+            t0 = int(fo.flat.step_ctr[0].item())
+            tab = self._tabulate(opts, i, t0, spe)
+            self.lr_tables[i] = tab
+            if tab is not None:
+                fo.set_table(tab, t0)
 
     def _refresh_flat_opts(self) -> bool:
         """Re-read every flat-kernel optimizer's param group (hooks may change lr, ...).
@@ -1259,6 +1361,101 @@ def _cpu_state(x):
     return x
 
 
+_MAX_LR_TABLE = 1 << 20  # entries of a tabulated scheduler (8 MiB of float64 on the device)
+
+
+def _parse_optimizers(ret):
+    """``configure_optimizers``' Lightning 1.5 forms -> (optimizers, scheduler records): an
+    optimizer; a list / tuple of optimizers; ``([optimizers], [schedulers])``; a dict
+    ``{"optimizer", "lr_scheduler": scheduler | {"scheduler", "interval", "frequency"}}``; a
+    tuple / list of such dicts.  A bare scheduler steps per epoch."""
+    Optimizer = torch.optim.Optimizer
+    opts, raw = [], []
+    if isinstance(ret, Optimizer):
+        opts = [ret]
+    elif isinstance(ret, dict):
+        ret = [ret]
+    if isinstance(ret, (list, tuple)) and not opts:
+        if len(ret) == 2 and all(isinstance(x, (list, tuple)) for x in ret) and \
+                all(isinstance(o, Optimizer) for o in ret[0]):
+            opts, raw = list(ret[0]), [{"scheduler": s} if not isinstance(s, dict) else s for s in ret[1]]
+        elif all(isinstance(x, dict) for x in ret):
+            for d in ret:
+                opts.append(d["optimizer"])
+                if "monitor" in d:
+                    raise NotImplementedError("configure_optimizers: 'monitor' (metric-driven schedulers) is not supported")
+                ls = d.get("lr_scheduler")
+                if ls is not None:
+                    raw.append(ls if isinstance(ls, dict) else {"scheduler": ls})
+        elif all(isinstance(x, Optimizer) for x in ret):
+            opts = list(ret)
+        else:
+            raise TypeError("configure_optimizers: an optimizer, a list of optimizers, ([optimizers], [schedulers]), "
+                            "a dict with 'optimizer' / 'lr_scheduler', or a tuple of such dicts")
+    recs = []
+    for d in raw:
+        s = d["scheduler"]
+        if "monitor" in d:
+            raise NotImplementedError("configure_optimizers: 'monitor' (metric-driven schedulers) is not supported")
+        if isinstance(s, torch.optim.lr_scheduler.ReduceLROnPlateau):
+            raise NotImplementedError("configure_optimizers: ReduceLROnPlateau (a metric-driven scheduler) is not "
+                                      "supported")
+        interval, freq = d.get("interval", "epoch"), int(d.get("frequency", 1))
+        if interval not in ("epoch", "step") or freq < 1:
+            raise ValueError(f"lr_scheduler: interval {interval!r} (epoch or step), frequency {freq} (>= 1)")
+        own = [i for i, o in enumerate(opts) if o is s.optimizer]
+        if not own:
+            raise ValueError("lr_scheduler: its optimizer is not among the returned optimizers")
+        recs.append({"scheduler": s, "interval": interval, "frequency": freq, "opt": own[0]})
+    # stepping order within a batch: the step-interval ones first, then the epoch's end
+    recs.sort(key=lambda r: r["interval"] == "epoch")
+    return opts, recs
+
+
+def _sched_due(r, done: int, spe, epoch_end: bool = False) -> bool:
+    if epoch_end:
+        return r["interval"] == "epoch" and done % r["frequency"] == 0
+    if r["interval"] == "step":
+        return done % r["frequency"] == 0
+    return spe is not None and done % spe == 0 and (done // spe) % r["frequency"] == 0
+
+
+def _tabulate_lr(opt, recs, t0: int, g0: int, total: int, spe):
+    """Step a deep copy of ``opt`` + its schedulers (parameters and state shared, not copied)
+    through batches g0 .. total - 1 as ``Trainer._advance_schedulers`` will step the real ones;
+    entry t0 + k is the rate of the k-th of them.  None if anything but lr moves (OneCycleLR's
+    cycle_momentum), lr is a tensor, there are several param groups, or a scheduler raises."""
+    if len(opt.param_groups) != 1 or isinstance(opt.param_groups[0].get("lr"), torch.Tensor):
+        return None
+    memo = {id(p): p for g in opt.param_groups for p in g["params"]}
+    for st in opt.state.values():
+        for v in (st.values() if isinstance(st, dict) else ()):
+            if isinstance(v, torch.Tensor):
+                memo[id(v)] = v
+    try:
+        o2, s2 = copy.deepcopy((opt, [r["scheduler"] for r in recs]), memo)
+    except Exception:  # noqa: BLE001 - a scheduler that cannot be copied is not tabulated
+        return None
+    rest = lambda o: _group_key(o)[:2] + _group_key(o)[3:]  # noqa: E731 - everything but lr
+    key0 = rest(o2)
+    vals = []
+    try:
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")  # "lr_scheduler.step() before optimizer.step()": no step is taken here
+            for g in range(g0, total):
+                vals.append(float(o2.param_groups[0]["lr"]))
+                for r, sc in zip(recs, s2):
+                    if _sched_due(r, g + 1, spe):
+                        sc.step()
+                if rest(o2) != key0:
+                    return None
+    except Exception:  # noqa: BLE001 - e.g. OneCycleLR stepped past its total_steps
+        return None
+    if not vals:
+        return None
+    return tuple([vals[0]] * t0 + vals)
+
+
 _GROUP_KEYS = ("lr", "betas", "eps", "weight_decay", "momentum", "dampening", "nesterov", "amsgrad", "maximize",
                "differentiable", "decoupled_weight_decay")
 
@@ -1312,6 +1509,10 @@ class _FlatTorchOptimizer:
         self.cfg = cfg
         self.flat = FlatOptimizer(flat_p, flat_g, cfg)
         self._key = _group_key(opt)
+        # a tabulated scheduler (Trainer._table_flat_opts): the kernel reads table[step counter];
+        # host_t mirrors the counter (advanced by the Trainer once per batch, replays included)
+        self.table: tuple | None = None
+        self.host_t = 0
         self._import_state()
 
     def _import_state(self):
@@ -1343,6 +1544,14 @@ class _FlatTorchOptimizer:
         key = _group_key(self.opt)
         if key == self._key:
             return False
+        if self.table is not None:
+            # the scheduler's own move of lr to the table's value is no hyperparameter edit
+            lr = self.opt.param_groups[0].get("lr")
+            if key[:2] + key[3:] == self._key[:2] + self._key[3:] and not isinstance(lr, torch.Tensor) and \
+                    float(lr) == self.table[min(self.host_t, len(self.table) - 1)]:
+                self._key = key
+                return False
+            self.table = None  # an edit from outside the schedule: back to the param group, re-read per batch
         self._key = key
         cfg = _optim_config(self.opt)
         if cfg is None or cfg.name != self.cfg.name:
@@ -1352,6 +1561,14 @@ class _FlatTorchOptimizer:
             return False
         self.cfg = self.flat.cfg = cfg
         return True
+
+    def set_table(self, values, t0: int) -> None:
+        from ..ops.schedule import LrSchedule
+
+        self.table, self.host_t = tuple(values), int(t0)
+        self.cfg = self.flat.cfg = dataclasses.replace(self.cfg, schedule=LrSchedule.from_values(self.table))
+        # the device copy is made here, never during a capture of the step
+        self.cfg.schedule.device_table(self.flat.params.device)
 
     def step(self, zero_grad: bool = False, fused=None) -> bool:
         return self.flat.step(zero_grad=zero_grad, fused=fused)
