@@ -117,8 +117,8 @@ def _compile(src: Path, verbose: bool, full: str) -> Path:
 
 def variant(name: str, flags: list[str], sources: tuple[str, ...] = ("mlp_train.hip",),
             verbose: bool = False) -> Path:
-    """A/B build: ``sources`` recompiled with extra ``flags`` (e.g. ``-DDTP_BWD_PK=0``)
-    into ``_lib/var_<name>/libdtp.so``, linked with the default objects of every other
+    """A/B build: ``sources`` recompiled with extra ``flags`` (e.g. ``-DDTP_ADAM_FAST=0`` with
+    ``sources=("mlp_train.hip", "optim.hip", ...)``: every source that includes ``optim_core.h``) into ``_lib/var_<name>/libdtp.so``, linked with the default objects of every other
     source.  Load it with ``DTP_LIB=<path>`` (``_native.LIB_PATH``)."""
     build(verbose=verbose)
     vdir = LIBDIR / f"var_{name}"

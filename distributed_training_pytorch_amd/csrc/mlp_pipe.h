@@ -1,9 +1,9 @@
 // Software-pipelined forward + backward of the fused train step (v6).
 //
-// Why: in the v5 step (mlp_scalar.h lds_forward / lds_backward_dx) every layer
-// reads its LDS weight block right before the FMAs that consume it.  The
-// compiler keeps those reads just ahead of their uses, so a wave -- alone on its
-// SIMD, nothing to switch to -- sits on ~90 `s_waitcnt lgkmcnt` per step, each
+// Why: in the step before it (v5, since removed) every layer read its LDS weight
+// block right before the FMAs that consume it.  The compiler kept those reads just
+// ahead of their uses, so a wave -- alone on its SIMD, nothing to switch to -- sat
+// on ~90 `s_waitcnt lgkmcnt` per step, each
 // exposing most of an LDS round trip (rocprofv3 + ISA listing, docs/perf_notes.md).
 //
 // Here a layer's block is already in registers when the layer starts: the

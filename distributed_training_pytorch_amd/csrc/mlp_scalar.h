@@ -34,10 +34,8 @@ struct Scal {
   }
   static constexpr int fbo(int l) { return fwo(l) + S::din(l) * pad2(S::dout(l)); }
   static constexpr int LF = fwo(NL);
-  // per-model global workspace (forward blocks only), 64-float (256 B) aligned;
-  // 64-byte scalar-cache lines it spans
+  // per-model global workspace (forward blocks only), 64-float (256 B) aligned
   static constexpr int WS = (LF + 63) & ~63;
-  static constexpr int NLINES = (LF + 15) / 16;
   // backward blocks live in LDS: W_l [out][pad4(in)], read as broadcast ds_read_b128
   static constexpr int pad4(int x) { return (x + 3) & ~3; }
   static constexpr int lbo(int l) {
@@ -115,104 +113,6 @@ DTP_DEV float4 row_quad(const float* __restrict__ p) {
   }
 }
 
-// forward of one sample from the LDS forward blocks: each layer's whole W^T block
-// (+ bias) is pulled out with broadcast ds_read_b128 (all in flight; LDS returns in
-// order, so the FMAs start as the first rows land), then consumed input-major:
-// every output pair is an independent v_pk_fma_f32 chain.
-template <class S>
-DTP_DEV void lds_forward(const float* __restrict__ wl, float (&h)[S::NL + 1][16], float slope) {
-  using SC = Scal<S>;
-  static_for<0, S::NL>([&](auto LC) {
-    constexpr int l = decltype(LC)::value;
-    constexpr int I = S::din(l), O = S::dout(l), OP = SC::pad4(O), NQ = OP / 4;
-    float4 bq[NQ];
-    float4 w4[I][NQ];
-    static_for<0, NQ>([&](auto QC) {
-      constexpr int q = decltype(QC)::value;
-      bq[q] = row_quad<O, q>(wl + SC::lfb(l));
-    });
-    static_for<0, I>([&](auto IC) {
-      constexpr int i = decltype(IC)::value;
-      static_for<0, NQ>([&](auto QC) {
-        constexpr int q = decltype(QC)::value;
-        w4[i][q] = row_quad<O, q>(wl + SC::lfo(l) + i * OP);
-      });
-    });
-    f32x2 z[2 * NQ];
-    static_for<0, NQ>([&](auto QC) {
-      constexpr int q = decltype(QC)::value;
-      z[2 * q] = f32x2{bq[q].x, bq[q].y};
-      z[2 * q + 1] = f32x2{bq[q].z, bq[q].w};
-    });
-    static_for<0, I>([&](auto IC) {
-      constexpr int i = decltype(IC)::value;
-      const f32x2 hi = f32x2{h[l][i], h[l][i]};
-      static_for<0, NQ>([&](auto QC) {
-        constexpr int q = decltype(QC)::value;
-        if constexpr (4 * q < O) z[2 * q] = __builtin_elementwise_fma(f32x2{w4[i][q].x, w4[i][q].y}, hi, z[2 * q]);
-        if constexpr (4 * q + 2 < O)
-          z[2 * q + 1] = __builtin_elementwise_fma(f32x2{w4[i][q].z, w4[i][q].w}, hi, z[2 * q + 1]);
-      });
-    });
-    static_for<0, O>([&](auto JC) {
-      constexpr int j = decltype(JC)::value;
-      const float v = (j & 1) ? z[j / 2].y : z[j / 2].x;
-      h[l + 1][j] = S::rnd(S::act(l) ? leaky(S::rnd(v), slope) : v);
-    });
-  });
-}
-
-// input gradient of layer l >= 1 for one sample: dz_{l-1} = (W_l^T dz_l) * act'(h_l).
-// The layer's whole row-major block is pulled out of LDS first (broadcast
-// ds_read_b128, all in flight at once: LDS returns in order, so the FMAs start
-// as soon as the first rows land), then consumed output-major with input pairs
-// as independent v_pk_fma_f32 chains.
-// MFMA interleave: a wave issues in order, and each v_mfma_f32_16x16x4_f32 holds
-// the MFMA pipe for 32 cycles, so the caller's NK MFMA K-steps are spread one or
-// two per weight row -- between two MFMAs the wave issues that row's ~5 FMAs
-// (the sched_group_barrier pipeline pins the MFMA/VALU alternation), and the
-// layer costs ~NK x 32 cycles instead of MFMA time + FMA time.
-template <class S, int l, int NK, class MfmaK>
-DTP_DEV void lds_backward_dx(const float* __restrict__ wl, const float (&h)[S::NL + 1][16], float (&dz)[16],
-                             float slope, MfmaK&& mfma_k) {
-  using SC = Scal<S>;
-  constexpr int I = S::din(l), O = S::dout(l), IP = SC::pad4(I), NQ = IP / 4;
-  float4 w4[O][NQ];
-  static_for<0, O>([&](auto JC) {
-    constexpr int j = decltype(JC)::value;
-    static_for<0, NQ>([&](auto QC) {
-      constexpr int q = decltype(QC)::value;
-      w4[j][q] = row_quad<I, q>(wl + SC::lbo(l) + j * IP);
-    });
-  });
-  f32x2 g[2 * NQ];
-  static_for<0, 2 * NQ>([&](auto QC) { g[decltype(QC)::value] = f32x2{0.f, 0.f}; });
-  static_for<0, O>([&](auto JC) {
-    constexpr int j = decltype(JC)::value;
-    constexpr int k0 = NK * j / O, k1 = NK * (j + 1) / O;
-    static_for<k0, k1>([&](auto KC) { mfma_k(KC); });
-    const f32x2 d = f32x2{dz[j], dz[j]};
-    static_for<0, NQ>([&](auto QC) {
-      constexpr int q = decltype(QC)::value;
-      if constexpr (4 * q < I) g[2 * q] = __builtin_elementwise_fma(f32x2{w4[j][q].x, w4[j][q].y}, d, g[2 * q]);
-      if constexpr (4 * q + 2 < I)
-        g[2 * q + 1] = __builtin_elementwise_fma(f32x2{w4[j][q].z, w4[j][q].w}, d, g[2 * q + 1]);
-    });
-    if constexpr (k1 > k0) {
-      constexpr int nv = (I + 1) / 2;  // this row's v_pk_fma_f32 count
-      static_for<k0, k1>([&](auto) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                  // 1 MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, nv / (k1 - k0), 0);     // then VALU
-      });
-    }
-  });
-  static_for<0, I>([&](auto IC) {
-    constexpr int i = decltype(IC)::value;
-    const float v = (i & 1) ? g[i / 2].y : g[i / 2].x;
-    dz[i] = S::rnd(S::rnd(v) * (S::act(l - 1) ? leaky_grad_from_out(h[l][i], slope) : 1.f));
-  });
-}
-
 // the wave's MFMA operands of one staged tile (see wave_outer_acc): 16 K-steps
 struct TileOps {
   float4 a[4], b[4];
@@ -236,20 +136,6 @@ DTP_DEV void tile_kstep(const TileOps& t, f32x4& acc0, f32x4& acc1) {
   const float bv = (K % 4 == 0) ? b.x : (K % 4 == 1) ? b.y : (K % 4 == 2) ? b.z : b.w;
   if constexpr (K & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc1, 0, 0, 0);
   else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc0, 0, 0, 0);
-}
-
-// K-steps [K0, K1) of the tile on two alternating accumulators
-template <int K0, int K1>
-DTP_DEV void tile_ksteps(const TileOps& t, f32x4& acc0, f32x4& acc1) {
-  static_for<K0, K1>([&](auto KC) {
-    constexpr int k = decltype(KC)::value;
-    const float4& a = t.a[k / 4];
-    const float4& b = t.b[k / 4];
-    const float av = (k % 4 == 0) ? a.x : (k % 4 == 1) ? a.y : (k % 4 == 2) ? a.z : a.w;
-    const float bv = (k % 4 == 0) ? b.x : (k % 4 == 1) ? b.y : (k % 4 == 2) ? b.z : b.w;
-    if constexpr (k & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc1, 0, 0, 0);
-    else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc0, 0, 0, 0);
-  });
 }
 
 // staging helper: write columns [c0, c0+n) of this lane's row (v1 [q][col][t] layout)

@@ -31,25 +31,8 @@ constexpr int kDataCache = 12288;
 // Adam bias-correction scalars of the next kAdamTab steps, formed cooperatively in
 // f64 (torch's host math) once per kAdamTab steps instead of per step
 constexpr int kAdamTab = 1024;
-#ifndef DTP_PIPE
-#define DTP_PIPE 1  // software-pipelined forward/backward (mlp_pipe.h); 0 = the v5 schedule
-#endif
 
 constexpr int kWaves = kBlock / kWave;
-
-#ifndef DTP_GRP_SPLIT
-#define DTP_GRP_SPLIT 1  // split-batch exchange: publisher / poller waves (grp_allreduce_split); 0: every thread both
-#endif
-#ifndef DTP_GRP_DIRECT
-// 1: the publisher wave sums its granules from the dW tiles itself (no staging, no barrier):
-// measured slower (3.70 vs 3.61 us/step: 24 scattered tile reads on the publisher's path
-// against one LDS round and a barrier, profiles/r5_exchange/direct_ab/)
-#define DTP_GRP_DIRECT 0
-#endif
-
-#ifndef DTP_XWAIT
-#define DTP_XWAIT 1  // 0 (A/B builds only): no exchange-wait diagnostic (bench exchange_wait_us_per_step)
-#endif
 
 // entries base + tid + j * kBlock (j < J) of the host's Adam table for a launch starting
 // at step t0: {lr / (1 - b1^t1), sqrt(1 - b2^t1)} with t1 = t0 + e + 1, clamped to the
@@ -73,7 +56,7 @@ DTP_DEV void adam_tab_store(float2* __restrict__ lds, int n, int tid, const floa
     if (tid + j * NTH < n) lds[tid + j * NTH] = v[j];
 }
 
-template <class S, bool XCH = false>
+template <class S>
 struct TrainSmem {
   float wb[Scal<S>::LW];  // backward + forward weight blocks (mlp_scalar.h)
   float2 adam_tab[kAdamTab];  // per-step Adam scalars {lr / (1 - b1^t), sqrt(1 - b2^t)}
@@ -85,8 +68,9 @@ struct TrainSmem {
   float data[kDataCache];
   float sink[4];  // target of the optimizer's predicated-off stores (slots past P)
   float lossw[kBlock / kWave];  // bf16 instances: per-wave batch-loss sums (not through a bf16 tile)
-  // xGMI instances: the split exchange's payloads (xgmi_allreduce_split)
-  alignas(16) float2 xg[XCH ? xgmi_split_lds_f2<S::P, S::NPT>() : 2];
+  // unused (what an xGMI exchange with LDS staging left behind): 16 bytes of every instance's
+  // LDS size, kept until a change that may alter the kernels' descriptors
+  alignas(16) float2 xg_stub[2];
 };
 
 // One lane's sample of a step: input, target (class index for CE) and validity.
@@ -115,17 +99,10 @@ struct SampleRegs {
 
 // Fused train step(s), one workgroup (4 waves, one lane per sample) per model.
 // Weights live in LDS blocks read into registers one layer ahead (mlp_pipe.h),
-// activations in VGPRs, the dW reduction
-// over the batch runs on MFMA through a per-wave LDS staging area, the optimizer
-// owns NPT parameters per thread in registers (params and moments).
-#ifndef DTP_TRAIN_WAVES_PER_EU
-#define DTP_TRAIN_WAVES_PER_EU 1  // one wave per SIMD: the scheduler may spend registers on latency
-#endif
-#if DTP_TRAIN_WAVES_PER_EU
-#define DTP_TRAIN_ATTR __attribute__((amdgpu_waves_per_eu(DTP_TRAIN_WAVES_PER_EU, DTP_TRAIN_WAVES_PER_EU)))
-#else
-#define DTP_TRAIN_ATTR
-#endif
+// activations in VGPRs, the dW reduction over the batch runs on MFMA through a per-wave
+// LDS staging area, the optimizer owns NPT parameters per thread in registers (params
+// and moments).  One wave per SIMD (amdgpu_waves_per_eu(1, 1)): the scheduler may spend
+// registers on latency.
 // FAST: the common configuration fixed at compile time (MSE, batch <= 256, the
 // SAMPLER_TABLE sampler -- the epoch permutations in a device ring the host fills
 // ahead, torch's exact DistributedSampler order by default --, dataset cached in LDS,
@@ -134,15 +111,15 @@ struct SampleRegs {
 // is straight-line LDS code the scheduler interleaves with the optimizer, and
 // LeakyReLU is max(z, slope z).
 template <class S, int MODE, bool PROF = false, bool FAST = false>
-__global__ __launch_bounds__(kBlock) DTP_TRAIN_ATTR void mlp_train_kernel(DtpTrainArgs a) {
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) void mlp_train_kernel(DtpTrainArgs a) {
   using SC = Scal<S>;
   constexpr int NL = S::NL, P = S::P, NT = SC::NT, NPT = S::NPT;
   static_assert(NT * SC::TSZ <= 2 * 2 * kStgArr, "a wave's reduction tiles must fit in its staging area");
-  __shared__ __align__(16) TrainSmem<S, DTP_XGMI_SPLIT && (MODE == DTP_MODE_XGMI_ADAM || MODE == DTP_MODE_XGMI_SGD)> sm;
+  static_assert(NL >= 3, "the pipelined forward / backward (mlp_pipe.h) keeps two layers in flight");
+  __shared__ __align__(16) TrainSmem<S> sm;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int model = blockIdx.x;
   constexpr bool kUpdate = MODE != DTP_MODE_GRAD;
-  constexpr bool kPipe = DTP_PIPE && S::NL >= 3;
   constexpr bool kAdam = MODE == DTP_MODE_ADAM || MODE == DTP_MODE_XGMI_ADAM;
   constexpr bool kXgmi = MODE == DTP_MODE_XGMI_ADAM || MODE == DTP_MODE_XGMI_SGD;
   unsigned long long* prof = reinterpret_cast<unsigned long long*>(a.status);
@@ -345,14 +322,11 @@ __global__ __launch_bounds__(kBlock) DTP_TRAIN_ATTR void mlp_train_kernel(DtpTra
       static_for<0, S::IN>([&](auto IC) { h[0][decltype(IC)::value] = smpl.x[decltype(IC)::value]; });
       BBlk<S, NL - 1> pbt;  // backward blocks prefetched by the pipelined forward
       TopB2<S> pbt2;
-      if constexpr (kPipe) {
+      {
         FBlk<S, 0> pb0;
         pb0.template load<0, FBlk<S, 0>::NR>(sm.wb);
         if (c0 == 0) DTP_STAMP(1);
         pipe_forward<S, 0, FAST>(sm.wb, pb0, h, slope, pbt, pbt2);
-      } else {
-        if (c0 == 0) DTP_STAMP(1);
-        lds_forward<S>(sm.wb, h, slope);
       }
 
       // ---------------- loss (MSE / CE) -> dz of the last layer
@@ -388,47 +362,8 @@ __global__ __launch_bounds__(kBlock) DTP_TRAIN_ATTR void mlp_train_kernel(DtpTra
       lacc += lpart;
 
       // ---------------- backward: dX chain (VALU, LDS weight blocks) + dW tiles (MFMA, K = samples)
-      if constexpr (kPipe) {
-        const PipeBwdCtx<S> pc{sm.wb, stg_pack, &sm.stage[wave][1][0], lane, slope, lpart};
-        pipe_backward<S>(pc, pbt, pbt2, h, dz, acc);
-      } else {
-      static_for<0, NL>([&](auto RC) {
-        constexpr int l = NL - 1 - decltype(RC)::value;
-        constexpr int I = S::din(l), O = S::dout(l);
-        constexpr bool packed = SC::PACK && (l == 0 || l == NL - 1);
-        float* stg = packed ? stg_pack : &sm.stage[wave][1][0];
-        float* dzb = stg;
-        float* hb = stg + kStgArr;
-        stage_cols<O>(dzb, lane, SC::rowoff(l), dz);
-        if constexpr (l == NL - 1) stage_one(dzb, lane, SC::lossrow(), lpart);
-        stage_cols<I>(hb, lane, SC::coloff(l), h[l]);
-        stage_one(hb, lane, SC::coloff(l) + I, 1.f);
-        if constexpr (l == 2) if (c0 == 0) DTP_STAMP(16);
-        if constexpr (!packed) {
-          // this layer's 16 MFMA K-steps ride between the dX rows (mlp_scalar.h)
-          __builtin_amdgcn_wave_barrier();
-          const TileOps to = tile_ops(dzb, hb, lane);
-          if constexpr (l == 2 && PROF) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::"v"(to.a[0].x), "v"(to.b[3].w));
-            if (c0 == 0) DTP_STAMP(17);
-          }
-          f32x4 a1 = f32x4{0.f, 0.f, 0.f, 0.f};
-          f32x4& a0 = acc[SC::tile(l)];
-          lds_backward_dx<S, l, 16>(sm.wb, h, dz, slope,
-                                    [&](auto KC) { tile_kstep<decltype(KC)::value>(to, a0, a1); });
-          a0 += a1;
-          __builtin_amdgcn_wave_barrier();
-        } else if constexpr (l > 0) {
-          lds_backward_dx<S, l, 0>(sm.wb, h, dz, slope, [](auto) {});
-        }
-        if (c0 == 0) DTP_STAMP(24 + l);
-      });
-      if constexpr (SC::PACK) {
-        __builtin_amdgcn_wave_barrier();
-        acc[0] = wave_outer_acc(stg_pack, stg_pack + kStgArr, acc[0], lane);
-        __builtin_amdgcn_wave_barrier();
-      }
-      }
+      const PipeBwdCtx<S> pc{sm.wb, stg_pack, &sm.stage[wave][1][0], lane, slope, lpart};
+      pipe_backward<S>(pc, pbt, pbt2, h, dz, acc);
     }
     if constexpr (S::BF) {
       const float wl = wave_sum(lacc);
@@ -472,14 +407,7 @@ __global__ __launch_bounds__(kBlock) DTP_TRAIN_ATTR void mlp_train_kernel(DtpTra
       // all-reduce (sum) this model's gradient + loss over every rank through
       // the peers' xGMI-mapped receive buffers, inside the step (xgmi_core.h)
       xepoch += 1u;
-#if DTP_XGMI_SPLIT
-      const XgmiCtx xc{a.peers, a.status, a.smp.world, a.smp.rank, a.n_models, a.timeout_us};
-      gloss = xgmi_allreduce_split<P, NPT, kBlock>(xc, model, g, mean_loss, xepoch, tid, sm.xg,
-                                                   sm.xg + xgmi_slot16(P, NPT), xdead, DTP_XWAIT ? xwait : nullptr);
-#else
-      gloss = xgmi_allreduce_model<NPT, kBlock>(a, model, P, g, mean_loss, xepoch, tid, DTP_XWAIT ? xwait : nullptr,
-                                                1, 0, &xdead);
-#endif
+      gloss = xgmi_allreduce_model<NPT, kBlock>(a, model, P, g, mean_loss, xepoch, tid, xwait, 1, 0, &xdead);
     }
 
     // advance the sampler / loss-ring position and gather the next step's first
@@ -561,7 +489,7 @@ __global__ __launch_bounds__(kBlock) DTP_TRAIN_ATTR void mlp_train_kernel(DtpTra
     }
     if (tid == 0) a.step[model] = t0 + a.n_steps;
     if (kXgmi && tid == 0) a.epoch[model] = xepoch;
-    if (DTP_XWAIT && kXgmi && model == 0 && a.status) xgmi_record_wait(a.status, xwait, (unsigned long long)a.n_steps, tid);
+    if (kXgmi && model == 0 && a.status) xgmi_record_wait(a.status, xwait, (unsigned long long)a.n_steps, tid);
     stamp_launch(21);
   }
 }
@@ -581,41 +509,6 @@ DTP_HD constexpr int lane_areas() { return Scal<S>::PACK ? 2 : 3; }
 template <class S>
 DTP_HD constexpr int lane_area(int l) {
   return (Scal<S>::PACK && (l == 0 || l == S::NL - 1)) ? 0 : (l == S::NL - 1 ? 0 : (l == 0 ? 2 : 1));
-}
-
-#ifndef DTP_LANE_OWN
-// 1: the several-lanes kernels' parameter ownership follows the forward blocks' LDS order
-// (lane_own_param) instead of torch order: consecutive lanes then write consecutive LDS
-// words in the post-Adam weight scatter and read consecutive tile slots in the cross-wave
-// gradient sums (torch order puts 5-8 lanes of a 32-lane group on one bank in both).
-// Measured SLOWER at batch 256 (split-batch step, K = 2000, 4 interleaved runs each:
-// 3.351-3.362 vs 3.320-3.331 us/step, profiles/r6_misc/r6j/): off
-#define DTP_LANE_OWN 0
-#endif
-
-// the torch-order parameter of ownership slot s (< P): the forward blocks' LDS order -- a
-// partitioned layer's block is rows r (inputs, then the bias row) of outputs j, the whole
-// last layer's rows j of inputs i (then its bias)
-template <class S>
-DTP_DEV int lane_own_param(int s) {
-  int p = s;
-  static_for<0, S::NL>([&](auto LC) {
-    constexpr int l = decltype(LC)::value;
-    constexpr int I = S::din(l), O = S::dout(l), base = S::gw(l), n = O * (I + 1);
-    if (s >= base && s < base + n) {
-      const int q = s - base;
-      int j, r;
-      if constexpr (l < S::NL - 1) {
-        r = q / O;
-        j = q - r * O;
-      } else {
-        j = q / (I + 1);
-        r = q - j * (I + 1);
-      }
-      p = r < I ? base + j * I + r : S::gb(l) + j;
-    }
-  });
-  return p;
 }
 
 // payload float of dW tile cell (tile t, row, col): the torch-order parameter whose gradient
@@ -655,7 +548,7 @@ constexpr bool lane_row_map_ok() {
   return true;
 }
 
-// ROWS: the per-wave partial dW sums are parked in payload order (grp_core.h, DTP_GRP_ROWS):
+// ROWS: the per-wave partial dW sums are parked in payload order (grp_core.h):
 // one row of grp_row_floats(P) floats per wave, then one sink float per lane for the tile
 // cells that hold no parameter
 template <class S, int L, int NW, bool GRP = false, bool ROWS = false>
@@ -669,10 +562,12 @@ struct LaneSmem {
   alignas(16) float2 adam_tab[kAdamTab];
   alignas(16) float data[kLaneData];
   float sink[4];
-  // split-batch exchange (grp_allreduce_split): this member's payloads, then every member's
+  // the exchanges' LDS, in float2: the on-chip one's (kGrpMax + 1) rows of grp_ps3(P) floats
+  // (grp_core.h) or the 3-float xGMI one's xgmi_g3_lds_floats(P) floats (xgmi_core.h)
+  // GSLOT: (kGrpMax + 1) slots of 2-float granules, which no exchange here stages in LDS any
+  // more; the term still sets the LDS size of the 3-layer, the 15-wide and the 8-wave
+  // split-batch instances, and stays until a change that may alter the kernels' descriptors
   static constexpr int GSLOT = xgmi_slot16(S::P, (S::P + 64 * NW - 1) / (64 * NW));
-  // (the 3-float form, DTP_GRP_G3: (kGrpMax + 1) rows of grp_ps3(P) floats)
-  // (the 3-float xGMI form, DTP_XGMI_G3: xgmi_g3_lds_floats(P) floats)
   static constexpr int GX2a = (kGrpMax + 1) * GSLOT > (kGrpMax + 1) * grp_ps3(S::P) / 2
                                   ? (kGrpMax + 1) * GSLOT : (kGrpMax + 1) * grp_ps3(S::P) / 2;
   static constexpr int GX2 = GX2a > xgmi_g3_lds_floats(S::P) / 2 ? GX2a : xgmi_g3_lds_floats(S::P) / 2;
@@ -702,23 +597,21 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   // GRP with kXgmi: ONE flat exchange over world x groups members (xgmi_core.h)
   static_assert(!CE || S::OUT >= 2, "cross-entropy needs >= 2 classes");
   constexpr int YD = CE ? 1 : S::OUT;  // target floats per sample (a class id for CE)
-  // the split exchanges' LDS: the split-batch step, and the xGMI instances of 4 waves (the
-  // 8-wave ones keep the single-role exchange: their LDS is full)
-  constexpr bool kXsplit = DTP_XGMI_SPLIT && NW == 4 && (MODE == DTP_MODE_XGMI_ADAM || MODE == DTP_MODE_XGMI_SGD);
-  // the 3-float cross-GPU exchange (xgmi_core.h:xgmi_allreduce_g3), 4-wave instances
-  constexpr bool kXg3 = DTP_XGMI_G3 && !kXsplit && NW == 4 && kXgmi;
-  // the split-batch members park their dW sums in payload-order rows (DTP_GRP_ROWS); the
-  // on-chip exchange publishes straight from them (1) or stages them as before (2)
-  constexpr bool kRows = GRP && DTP_GRP_ROWS != 0;
-  constexpr bool kRowsPub = kRows && DTP_GRP_ROWS == 1 && !kXgmi && DTP_GRP_SPLIT && DTP_GRP_G3;
-  static_assert(!kRows || !DTP_LANE_OWN, "the rows hold payload float f = ownership slot f in torch order");
-  static_assert(!kRows || (!DTP_GRP_DIRECT && !DTP_GRP_DIRECT3), "the direct A/B paths index the tile layout");
+  // the 3-float cross-GPU exchange (xgmi_core.h:xgmi_allreduce_g3), 4-wave instances (the
+  // 8-wave ones keep the 2-float owner-thread exchange: their LDS is full)
+  constexpr bool kXg3 = NW == 4 && kXgmi;
+  // the split-batch members park their dW sums in payload-order rows; the on-chip exchange
+  // publishes straight from them and forms the own sums inside (grp_core.h)
+  constexpr bool kRows = GRP;
+  constexpr bool kRowsPub = kRows && !kXgmi;
   static_assert(!kRows || lane_row_map_ok<S>(), "tile cells -> payload floats: a bijection onto [0, P]");
   static_assert(GRC == 0 || (GRP && !kXgmi && GRC >= 2 && GRC <= kGrpMax), "a constant member count: on-chip exchange");
-  // the per-step tail of the on-chip split-batch instances with fewer instructions (DTP_GRP_DIET)
-  constexpr bool kDiet = GRP && !kXgmi && DTP_GRP_SPLIT && DTP_GRP_G3 && DTP_GRP_DIET != 0;
+  // the per-step tail of the on-chip split-batch instances with fewer instructions on the
+  // serial path behind the backward (one wave per SIMD: every instruction is an issue slot):
+  // the same floating-point operations in the same order, the same loads, stores and barriers
+  constexpr bool kDiet = GRP && !kXgmi;
   constexpr int kLossPos = kRows ? grp_row_pos(P) : SC::losspos();  // a wave's loss in sm.red[wave]
-  using Smem = LaneSmem<S, L, NW, GRP || kXsplit || kXg3, kRows>;
+  using Smem = LaneSmem<S, L, NW, GRP || kXg3, kRows>;
   __shared__ __align__(16) Smem sm;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int model = GRP ? (int)(blockIdx.x & 7u) : (int)blockIdx.x;
@@ -760,48 +653,17 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   // ---- prologue (all global reads issued before the first wait, as in mlp_train_kernel)
   float* __restrict__ gp = a.params + (size_t)model * P;
   const SamplerCfg smp = a.smp;
-  int pf[NPT], pb[NPT], tp[NPT], pown[NPT];
+  int pf[NPT], pb[NPT], tp[NPT];
   float pw[NPT], mr[NPT], vr[NPT];
 #pragma unroll
   for (int k = 0; k < NPT; ++k) {
-    const int s_ = NPT * tid + k;  // ownership slot (the exchanges' payload index)
-    const bool own = s_ < P;
-    const int p = DTP_LANE_OWN ? (own ? lane_own_param<S>(s_) : 0) : s_;
-    pown[k] = p;
+    const int p = NPT * tid + k;  // blocked ownership in torch order (the exchanges' payload index)
+    const bool own = p < P;
     lane_pos<C, S>(own ? p : 0, pf[k], pb[k], tp[k]);
-    if constexpr (kRows) tp[k] = own ? grp_row_pos(s_) : 0;  // its sums come from the rows
+    if constexpr (kRows) tp[k] = own ? grp_row_pos(p) : 0;  // its sums come from the rows
     pw[k] = own ? gp[p] : 0.f;
     mr[k] = own ? a.opt_m[(size_t)model * P + p] : 0.f;
     vr[k] = (kAdam && own) ? a.opt_v[(size_t)model * P + p] : 0.f;
-  }
-  // split-batch publisher (wave 0, DTP_GRP_DIRECT): the dW-tile positions of the parameters of
-  // its granules q = tid + 64 j (granule q holds parameters NPT (q / GPT) + 2 (q % GPT), + 1;
-  // the last granule is the loss), so it sums them straight from the tiles
-  constexpr int kGpt = xgmi_gpt<NPT>(), kNg = xgmi_nthr(P, NPT) * kGpt + 1, kPubJ = (kNg + kWave - 1) / kWave;
-  int gtp[GRP && DTP_GRP_DIRECT ? kPubJ : 1][2];
-  if constexpr (GRP && DTP_GRP_DIRECT) {
-#pragma unroll
-    for (int j = 0; j < kPubJ; ++j) {
-      const int q = tid + j * kWave;
-      const int p0 = (q / kGpt) * NPT + 2 * (q % kGpt);
-      const bool two = 2 * (q % kGpt) + 1 < NPT;
-      int pf_, pb_;
-      lane_pos<C, S>(p0 < P ? p0 : 0, pf_, pb_, gtp[j][0]);
-      lane_pos<C, S>((two && p0 + 1 < P) ? p0 + 1 : 0, pf_, pb_, gtp[j][1]);
-    }
-  }
-  // split-batch direct publish (DTP_GRP_DIRECT3): the dW-tile positions of the payload floats
-  // 3 tid .. 3 tid + 2 of granule tid (a parameter's tile slot, the loss slot, or -1: the XCC
-  // id / padding)
-  int gt3[GRP && DTP_GRP_DIRECT3 ? 3 : 1];
-  if constexpr (GRP && DTP_GRP_DIRECT3) {
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const int f = 3 * tid + i;
-      int pf_, pb_, t_;
-      lane_pos<C, S>(f < P ? f : 0, pf_, pb_, t_);
-      gt3[i] = f < P ? t_ : (f == P ? SC::losspos() : -1);
-    }
   }
   // row layout: where each of this lane's 4 NT accumulator elements is parked (its payload
   // float's place in the wave's row, or the lane's sink float), fixed for the launch
@@ -847,7 +709,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   unsigned xepoch = kXgmi ? a.epoch[model] : (GRP ? a.grp_epoch[model] : 0u);  // GRP + xGMI: the xGMI epochs
   // one model per workgroup: the epoch is the same on every lane (its parity selects the
   // exchange buffer's half through a scalar offset, grp_core.h)
-  if constexpr (kDiet && (DTP_GRP_DIET & 4)) xepoch = (unsigned)__builtin_amdgcn_readfirstlane((int)xepoch);
+  if constexpr (kDiet) xepoch = (unsigned)__builtin_amdgcn_readfirstlane((int)xepoch);
   // the exchanges' sticky timeout flag, read once per launch with the prologue loads
   const int* xst = kXgmi ? a.status : (GRP ? a.grp_status : nullptr);
   bool xdead = xst ? (__hip_atomic_load(xst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) : false;
@@ -882,8 +744,8 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     }
   }
   stamp_launch(22);
-  // DTP_GRP_DIET & 2: where the weight scatter after the optimizer writes, as float offsets
-  // into sm, fixed for the launch: the parameter's forward and backward copies, or the sink
+  // kDiet: where the weight scatter after the optimizer writes, as float offsets into sm,
+  // fixed for the launch: the parameter's forward and backward copies, or the sink
   // floats for a slot this thread does not own (the last owner of an odd P owns one of two)
   // or a parameter without a backward copy
   constexpr int kSinkOff = (int)(offsetof(Smem, sink) / sizeof(float));
@@ -896,7 +758,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     wo[k][1] = own && pb[k] >= 0 ? pb[k] : kSinkOff + 1;
   }
   int lslot = a.loss_log ? t0 % a.loss_log_cap : 0;
-  // DTP_GRP_DIET & 32: the loss log as a running element offset (lslot * n_models + model,
+  // kDiet: the loss log as a running element offset (lslot * n_models + model,
   // advanced by n_models per step, wrapped at the ring's end), one per-launch predicate for
   // its store, and the Adam table's refill counted down
   const bool llog = tid == ((kXgmi || GRP) ? xgmi_loss_tid<NPT>(P, NTH) : 0) && a.loss_log && lead;
@@ -1165,80 +1027,29 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       for (int ww = 0; ww < NW; ++ww) ls += sm.red[ww][kLossPos];
       lsum = ls;
     };
-    // the split-batch step's direct publish forms these inside the exchange
-    constexpr bool kDefer = (GRP && !kXgmi && DTP_GRP_SPLIT && DTP_GRP_G3 && DTP_GRP_DIRECT3) || kRowsPub;
-    if constexpr (!kDefer) own_sums();
-    // the next step's sample and the index of the one after it (independent of this step's
-    // exchange: the split-batch step runs it inside the exchange's waits)
+    // the next step's sample and the index of the one after it (run behind the exchanges)
     const int lslot_now = lslot;
     auto next_sample = [&]() {
       roll(epoch, bi);
-      if constexpr (!(kDiet && (DTP_GRP_DIET & 32))) {
+      if constexpr (!kDiet) {
         if (a.loss_log && ++lslot == a.loss_log_cap) lslot = 0;
       }
       nvalid = fast_gather(fidx, nx, ny);
       roll(e2, b2);
       fidx = fast_index(e2, b2);
     };
-    bool sampled = false;
-    if constexpr (GRP && !kXgmi) {  // the members' partial sums, on chip (grp_core.h)
+    if constexpr (!kRowsPub) {
+      own_sums();
+    } else {  // the members' partial sums, on chip (grp_core.h): published from the rows, own_sums
+              // runs inside the exchange (wave order: the same bits)
       xepoch += 1u;
       GrpProf gp_;
-#if DTP_GRP_SPLIT && DTP_GRP_DIRECT
-      auto pubval = [&](int j) -> float2 {  // granule tid + 64 j of this member, from the tiles
-        float x = 0.f, y = 0.f;
-        if (tid + j * kWave == kNg - 1) {
-#pragma unroll
-          for (int ww = 0; ww < NW; ++ww) x += sm.red[ww][SC::losspos()];
-        } else {
-#pragma unroll
-          for (int ww = 0; ww < NW; ++ww) {
-            x += sm.red[ww][gtp[j][0]];
-            y += sm.red[ww][gtp[j][1]];
-          }
-        }
-        return make_float2(x, y);
-      };
-      lsum = grp_allreduce_split<P, NPT, NTH>(gctx, model, g, lsum, xepoch, tid, xdead, sm.gx,
-                                              sm.gx + xgmi_slot16(P, NPT), xcc, gplain, PROF ? &gp_ : nullptr,
-                                              pubval);
-#elif DTP_GRP_SPLIT && DTP_GRP_G3 && DTP_GRP_DIRECT3
-      // granule q = tid: payload floats 3q .. 3q + 2 summed over the waves' parked tiles in
-      // wave order (own_sums' order: the published values are the bits this member adds)
-      auto pub3 = [&](int q, float (&v)[3]) {
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-          const int pos = gt3[i] >= 0 ? gt3[i] : 0;
-          float s_ = 0.f;
-#pragma unroll
-          for (int ww = 0; ww < NW; ++ww) s_ += sm.red[ww][pos];
-          const int f = 3 * q + i;
-          v[i] = f == P + 1 ? __uint_as_float(xcc) : (gt3[i] >= 0 ? s_ : 0.f);
-        }
-      };
-      lsum = grp_allreduce_split3d<P, NPT, NTH>(gctx, model, g, lsum, xepoch, tid, xdead,
-                                                reinterpret_cast<float*>(sm.gx), xcc, gplain,
-                                                PROF ? &gp_ : nullptr, pub3, own_sums);
-#elif DTP_GRP_SPLIT && DTP_GRP_G3
-      if constexpr (kRowsPub) {  // published from the rows; own_sums runs inside (wave order: the same bits)
-        lsum = grp_allreduce_rows3<P, NPT, NTH, GRC, NW, Smem::RSTR>(gctx, model, g, lsum, xepoch, tid, xdead,
-                                                                     reinterpret_cast<float*>(sm.gx), xcc, gplain,
-                                                                     PROF ? &gp_ : nullptr, &sm.red[0][0], own_sums);
-      } else {
-        lsum = grp_allreduce_split3<P, NPT, NTH, GRC>(gctx, model, g, lsum, xepoch, tid, xdead,
-                                                      reinterpret_cast<float*>(sm.gx), xcc, gplain,
-                                                      PROF ? &gp_ : nullptr, next_sample);
-        sampled = DTP_GRP_OVERLAP;
-      }
-#elif DTP_GRP_SPLIT
-      lsum = grp_allreduce_split<P, NPT, NTH>(gctx, model, g, lsum, xepoch, tid, xdead, sm.gx,
-                                              sm.gx + xgmi_slot16(P, NPT), xcc, gplain, PROF ? &gp_ : nullptr);
-#else
-      lsum = grp_allreduce<NPT, NTH>(gctx, model, P, g, lsum, xepoch, tid, xdead, PROF ? &gp_ : nullptr);
-#endif
-      if constexpr (PROF) {  // thread 0 (split: thread 64, a poller): publish issued (16), first poll consumed
-                             // (17), last granule (31), polls (30)
-        if (tid == (DTP_GRP_SPLIT ? 64 : 0) && it < 8) {
+      lsum = grp_allreduce_rows3<P, NPT, NTH, GRC, NW, Smem::RSTR>(gctx, model, g, lsum, xepoch, tid, xdead,
+                                                                   reinterpret_cast<float*>(sm.gx), xcc, gplain,
+                                                                   PROF ? &gp_ : nullptr, &sm.red[0][0], own_sums);
+      if constexpr (PROF) {  // thread 64, a poller: publish issued (16), first poll consumed (17), last
+                             // granule (31), polls (30)
+        if (tid == 64 && it < 8) {
           unsigned long long* pr = prof + ((size_t)blockIdx.x * 8 + it) * 32;
           pr[16] = gp_.t_pub;
           pr[17] = gp_.t_first;
@@ -1246,7 +1057,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
           pr[30] = gp_.polls;
           pr[15] = gp_.rt_end;  // chip-wide clock: this member's last granule
         }
-        if (DTP_GRP_SPLIT && tid == 0 && it < 8)  // the publisher: chip-wide clock when its stores were issued
+        if (tid == 0 && it < 8)  // the publisher: chip-wide clock when its stores were issued
           prof[((size_t)blockIdx.x * 8 + it) * 32 + 14] = gp_.rt_pub;
       }
     }
@@ -1258,18 +1069,13 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       if constexpr (kXg3) {
         const XgmiCtx xc{a.peers, a.status, a.smp.world, a.smp.rank, a.n_models, a.timeout_us};
         gloss = xgmi_allreduce_g3<P, NPT, NTH>(xc, model, g, mean_loss, xepoch, tid, reinterpret_cast<float*>(sm.gx),
-                                               xdead, DTP_XWAIT ? xwait : nullptr, GRP ? a.groups : 1, gk);
-      } else if constexpr (kXsplit) {
-        const XgmiCtx xc{a.peers, a.status, a.smp.world, a.smp.rank, a.n_models, a.timeout_us};
-        gloss = xgmi_allreduce_split<P, NPT, NTH>(xc, model, g, mean_loss, xepoch, tid, sm.gx,
-                                                  sm.gx + xgmi_slot16(P, NPT), xdead, DTP_XWAIT ? xwait : nullptr,
-                                                  GRP ? a.groups : 1, gk);
+                                               xdead, xwait, GRP ? a.groups : 1, gk);
       } else {
-        gloss = xgmi_allreduce_model<NPT, NTH>(a, model, P, g, mean_loss, xepoch, tid, DTP_XWAIT ? xwait : nullptr,
-                                               GRP ? a.groups : 1, gk, &xdead);
+        gloss = xgmi_allreduce_model<NPT, NTH>(a, model, P, g, mean_loss, xepoch, tid, xwait, GRP ? a.groups : 1, gk,
+                                               &xdead);
       }
     }
-    if (!sampled) next_sample();
+    next_sample();
     {
       AdamScalars as = adam_consts(a.hp);
       as.step_size = adam_sc.x;
@@ -1284,7 +1090,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       for (int k = 0; k < NPT; ++k) {
         const bool own = NPT * tid + k < P;
         const float wv = S::rnd(pw[k]);
-        if constexpr (kDiet && (DTP_GRP_DIET & 2)) {
+        if constexpr (kDiet) {
           float* const smf = reinterpret_cast<float*>(&sm);
           smf[wo[k][0]] = wv;
           smf[wo[k][1]] = wv;
@@ -1296,8 +1102,8 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     }
     // the thread that holds the summed loss logs it (the loss granule's owner: every other
     // thread of a split-batch member only has its own member's share)
-    if constexpr (kDiet && (DTP_GRP_DIET & 32)) {
-      if (llog) a.loss_log[loff] = kXgmi ? gloss * a.hp.grad_scale : mean_loss;
+    if constexpr (kDiet) {
+      if (llog) a.loss_log[loff] = mean_loss;
       loff += a.n_models;
       loff = loff >= lend ? loff - lend : loff;
     } else if (tid == ((kXgmi || GRP) ? xgmi_loss_tid<NPT>(P, NTH) : 0) && a.loss_log && lead) {
@@ -1306,7 +1112,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     }
     DTP_STAMP(6);
     __syncthreads();
-    if constexpr (kDiet && (DTP_GRP_DIET & 32)) {
+    if constexpr (kDiet) {
       if ((kAdam || ltab) && --refill == 0 && it + 1 < a.n_steps) {
         refill = kAdamTab;
         fill_adam(it + 1);
@@ -1329,8 +1135,8 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   if (!lead) return;  // every member holds the same state: the first writes it back
 #pragma unroll
   for (int k = 0; k < NPT; ++k) {
-    const int p = pown[k];
-    if (NPT * tid + k < P) {
+    const int p = NPT * tid + k;
+    if (p < P) {
       gp[p] = pw[k];
       a.opt_m[(size_t)model * P + p] = mr[k];
       if (kAdam) a.opt_v[(size_t)model * P + p] = vr[k];
@@ -1339,7 +1145,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   if (tid == 0) a.step[model] = t0 + a.n_steps;
   if (kXgmi && tid == 0) a.epoch[model] = xepoch;
   if (GRP && !kXgmi && tid == 0) a.grp_epoch[model] = xepoch;
-  if (DTP_XWAIT && kXgmi && model == 0 && a.status) xgmi_record_wait(a.status, xwait, (unsigned long long)a.n_steps, tid);
+  if (kXgmi && model == 0 && a.status) xgmi_record_wait(a.status, xwait, (unsigned long long)a.n_steps, tid);
   stamp_launch(21);
 }
 
@@ -1436,10 +1242,10 @@ void launch_lanes_grp(const DtpTrainArgs& a, hipStream_t st) {
 }
 
 // the on-chip split-batch instance of gr members: 4 members (batch 256 on one rank) have the
-// count as a constant (DTP_GRP_GRC), every other count reads it from the arguments
+// count as a constant, every other count reads it from the arguments
 template <class S, int MODE, bool CE = false>
 TrainLaunchFn grp_members(int gr) {
-  if (DTP_GRP_GRC && gr == 4) return &launch_lanes_grp<S, 4, 4, false, MODE, CE, 4>;
+  if (gr == 4) return &launch_lanes_grp<S, 4, 4, false, MODE, CE, 4>;
   return &launch_lanes_grp<S, 4, 4, false, MODE, CE>;
 }
 
@@ -1549,7 +1355,7 @@ int xgmi_max_slot16(int P) {
 // on 64 samples, their gradients summed on chip.  DTP_GROUPS=1 turns it off (A/B runs).
 // DTP_GROUPS: unset = the measured policy below, "on" = wherever an instance exists,
 // "off" / "0" / "1" = never (A/B runs)
-int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow, bool fast1) {
+int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow) {
   static const int env = [] {  // -1 policy, 0 off, 1 on
     const char* e = getenv("DTP_GROUPS");
     if (!e) return -1;
@@ -1561,7 +1367,7 @@ int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow, bool fast1) 
   const int want = env >= 0 ? env : (a.groups > 0 ? 1 : (a.groups < 0 ? 0 : -1));
   if (!allow || want == 0 || forced_lanes || a.n_models > 8) return 1;
   if (a.smp.n * (in + out) > dtp::kLaneData) return 1;
-  // the split-batch step keeps its loss-log position as a 32-bit element offset (DTP_GRP_DIET)
+  // the split-batch step keeps its loss-log position as a 32-bit element offset
   if (a.loss_log && (long long)a.loss_log_cap * a.n_models > 0x7fff0000LL) return 1;
   const int b = min(a.smp.batch, a.smp.num_samples);
   if (b <= 64) return 1;
@@ -1573,7 +1379,6 @@ int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow, bool fast1) 
   // the policy (docs/perf_notes.md "Round 5: the split-batch step"): on for 4 members per
   // model (per-rank batch 256 -- one rank: 3.35-3.40 vs 4.11 us/step, two ranks: 5.6 vs 6.2-6.6 in
   // the rehearsal); 2 members (batch 128) measured no better than the 2-lanes step
-  (void)fast1;
   return gr >= 4 ? gr : 1;
 }
 
@@ -1609,7 +1414,7 @@ TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int ou
   const bool ce = a.loss == DTP_LOSS_CE;
   LanePick lp = pick_lanes(a, in, out, base);
   if (base) {
-    const int gr = pick_groups(a, in, out, allow_groups, fast);
+    const int gr = pick_groups(a, in, out, allow_groups);
     // A/B only (DTP_GRP_NW=8): the split-batch step on members of 128 samples, each the
     // two-waves-per-SIMD 4-lanes step (8 waves), half the members of the default -- toy
     // fp32 Adam + MSE at one rank (docs/perf_notes.md "Round 6: two members")
@@ -1841,8 +1646,8 @@ int dtp_train_engine_profile(void* h, int n_steps, int t0, void* prof, void* str
   a.n_steps = n_steps;
   a.host_t0 = t0;
   a.status = static_cast<int*>(prof);
-  // the instance the engine runs: 4 members as a constant (DTP_GRP_GRC), else the run-time count
-  if (DTP_GRP_GRC && e->pick.GR == 4 && e->pick.NW == 4)
+  // the instance the engine runs: 4 members as a constant, else the run-time count
+  if (e->pick.GR == 4 && e->pick.NW == 4)
     launch_lanes_grp<dtp::Stage<2, 10, 5, 1, false>, 4, 4, true, DTP_MODE_ADAM, false, 4>(a, (hipStream_t)stream);
   else
     launch_lanes_grp<dtp::Stage<2, 10, 5, 1, false>, 4, 4, true>(a, (hipStream_t)stream);

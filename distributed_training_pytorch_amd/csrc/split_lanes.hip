@@ -570,8 +570,7 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
     if (use_dp) {
       gloss = xgmi_allreduce_g3<P, NPT, NTH>(xc, 0, g, gloss, ep, tid, sm.xg, xdead, nullptr, M, gk);
     } else if (M > 1) {
-      lsum = grp_allreduce_split3<P, NPT, NTH>(gctx, 0, g, lsum, ep, tid, xdead, sm.xg, xcc, gplain, nullptr,
-                                               [] {});
+      lsum = grp_allreduce_split3<P, NPT, NTH>(gctx, 0, g, lsum, ep, tid, xdead, sm.xg, xcc, gplain, nullptr);
       gloss = lsum * inv;
     }
     if (plain_ok && it == 0) {  // the readers' hello granules (sent in their prologues)

@@ -28,27 +28,8 @@
 
 namespace dtp {
 
-DTP_DEV unsigned long long pack_granule(unsigned epoch, float v) {
-  return ((unsigned long long)epoch << 32) | (unsigned long long)__float_as_uint(v);
-}
-
-DTP_DEV void store_granule_sys(unsigned long long* p, unsigned long long g) {
-  __hip_atomic_store(p, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-DTP_DEV unsigned long long load_granule_sys(const unsigned long long* p) {
-  return __hip_atomic_load(const_cast<unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // largest world the in-kernel exchange serves (one node: 8 GPUs, 7 xGMI links each)
 constexpr int kXgmiMaxWorld = 8;
-
-#ifndef DTP_XGMI_PIPE_POLL
-// 1: software-pipelined polls (next poll in flight while the previous one is checked).
-// Measured slower in the one-GPU rehearsal (2 ranks 7.6 vs 6.6 us/step, 8 ranks 12.4 vs
-// 10.0; profiles/r2_s3/ab_poll.txt), so the default is the plain poll-wait-check-sleep loop.
-#define DTP_XGMI_PIPE_POLL 0
-#endif
 
 // ---- fused-step exchange: 16-byte granules -----------------------------------
 // The fused train step owns its parameters in blocks: thread t holds parameters
@@ -205,32 +186,6 @@ DTP_DEV float xgmi_allreduce_slots(const XgmiCtx& a, int model, int P, float (&g
     }
     return true;
   };
-#if DTP_XGMI_PIPE_POLL
-  // Software-pipelined polling: the next poll is in flight while the previous one is
-  // checked (the compiler's vmcnt waits only for the older loads), so a granule is
-  // seen about one memory round trip after it lands instead of up to two.  A poll
-  // issued for a granule that an older poll already accepted is simply ignored.
-  if (pending && !dead) {
-    u32x4 xa[kXgmiMaxWorld][GPT + 1], xb[kXgmiMaxWorld][GPT + 1];
-    issue(xa, pending);
-    while (true) {
-      issue(xb, pending);
-      consume(xa);
-      if (!pending) break;
-      if (expired()) {
-        dead = true;
-        break;
-      }
-      issue(xa, pending);
-      consume(xb);
-      if (!pending) break;
-      if (expired()) {
-        dead = true;
-        break;
-      }
-    }
-  }
-#else
   while (pending && !dead) {
     u32x4 x[kXgmiMaxWorld][GPT + 1];
     issue(x, pending);
@@ -242,7 +197,6 @@ DTP_DEV float xgmi_allreduce_slots(const XgmiCtx& a, int model, int P, float (&g
     }
     __builtin_amdgcn_s_sleep(1);
   }
-#endif
   if (waited) {
     waited[0] += __builtin_amdgcn_s_memrealtime() - t_pub;
     waited[1] += t_pub - t_pub0;
@@ -262,157 +216,6 @@ DTP_DEV float xgmi_allreduce_slots(const XgmiCtx& a, int model, int P, float (&g
   return lacc;
 }
 
-#ifndef DTP_XGMI_SPLIT
-// 1: the fused steps' xGMI exchange with publisher / poller waves (xgmi_allreduce_split).
-// Off: in the one-GPU multi-rank rehearsal it measured slower (W = 2 / 4 / 8: 5.65 / 6.58 /
-// 9.00 vs 5.60 / 6.40 / 8.04 us/step, profiles/r5_exchange/), the single publisher wave
-// issuing (W - 1) x 187 stores at W = 8.  The on-chip split-batch exchange keeps its split
-// (grp_core.h), where it measured faster.
-#define DTP_XGMI_SPLIT 0
-#endif
-#ifndef DTP_XGMI_PUB_WAVES
-#define DTP_XGMI_PUB_WAVES 1  // waves that publish (the rest poll)
-#endif
-
-// LDS of the split exchange: this member's payloads [slot], then every virtual member's [8][slot]
-template <int P, int NPT>
-DTP_HD constexpr int xgmi_split_lds_f2() {
-  return (1 + kXgmiMaxWorld) * xgmi_slot16(P, NPT);
-}
-
-// The same all-reduce with the roles split over the waves, as grp_allreduce_split
-// (grp_core.h): gfx9 counts loads and stores in ONE in-order vmcnt, so a thread that polls
-// right after its own publish stores cannot consume its first poll before those stores --
-// posted xGMI writes to every peer -- are acknowledged.  Here the first DTP_XGMI_PUB_WAVES
-// waves publish every granule of this (virtual) member to every rank that reads it, the
-// other waves poll, and the payloads meet in LDS (two barriers).  Sums run in slot order, so
-// the result is bitwise that of xgmi_allreduce_slots.  waited: the polling thread's wait
-// (publish -> last granule accepted, s_memrealtime ticks), for the bench diagnostic.
-template <int P, int NPT, int NTHREADS>
-DTP_DEV float xgmi_allreduce_split(const XgmiCtx& a, int model, float (&g)[NPT], float loss, unsigned epoch, int tid,
-                                   float2* __restrict__ pub, float2* __restrict__ peer, bool& dead,
-                                   unsigned long long* waited = nullptr, int GR = 1, int gk = 0) {
-  constexpr int GPT = xgmi_gpt<NPT>();
-  constexpr int NPUB = kWave * DTP_XGMI_PUB_WAVES;          // publisher lanes
-  constexpr int NPOLL = NTHREADS - NPUB;                     // poller lanes
-  static_assert(NPOLL >= kWave, "at least one poller wave");
-  constexpr int slot = xgmi_slot16(P, NPT);
-  constexpr int nthr = xgmi_nthr(P, NPT);
-  constexpr int ng = nthr * GPT + 1;                         // granules of a member: gradients + the loss
-  constexpr int ltid = xgmi_loss_tid<NPT>(P, NTHREADS);
-  const int V = a.world * GR, R = a.rank * GR + gk;          // virtual members (slots), this member's slot
-  const size_t base = (size_t)((int)(epoch & 1u) * a.n_models + model) * V;
-  const bool has_g = tid < nthr;
-#pragma unroll
-  for (int k = 0; k < GPT; ++k)
-    if (has_g) pub[tid * GPT + k] = make_float2(2 * k < NPT ? g[2 * k] : 0.f, 2 * k + 1 < NPT ? g[2 * k + 1] : 0.f);
-  if (tid == ltid) pub[nthr * GPT] = make_float2(loss, 0.f);
-  __syncthreads();
-  if (tid < NPUB) {
-    // publish: every granule once into every rank's buffer that has a reader of this slot
-    // (this rank's own buffer too when other members of the rank read it)
-    for (int r = 0; r < a.world; ++r) {
-      if (r == a.rank && GR == 1) continue;
-      const __amdgpu_buffer_rsrc_t rs = xgmi_rsrc(a.peers[r]);
-      for (int q = tid; q < ng; q += NPUB) {
-        const float2 v = pub[q];
-        const uint32_t x0 = __float_as_uint(v.x), x1 = __float_as_uint(v.y);
-        const u32x4 qq = {epoch, x0, x1, xgmi_check(epoch, x0, x1)};
-        __builtin_amdgcn_raw_buffer_store_b128(qq, rs, (int)(((base + R) * slot + q) * 16), 0, kSysCoherent);
-      }
-    }
-  } else {
-    // poll the other V - 1 slots of the local buffer: item i = (slot index i / ng, granule
-    // i % ng), at most MAXI per lane, all requested at once, only the missing ones re-polled
-    constexpr int MAXI = ((kXgmiMaxWorld - 1) * ng + NPOLL - 1) / NPOLL;
-    static_assert(MAXI <= 32, "pending mask");
-    const __amdgpu_buffer_rsrc_t ms = xgmi_rsrc(a.peers[a.rank]);
-    const int pl = tid - NPUB;
-    const int total = (V - 1) * ng;
-    int off[MAXI], dst[MAXI];
-    uint32_t pending = 0u;
-#pragma unroll
-    for (int j = 0; j < MAXI; ++j) {
-      const int i = pl + j * NPOLL;
-      const int vi = i / ng, q = i - vi * ng;
-      const int v = vi < R ? vi : vi + 1;
-      off[j] = (int)(((base + v) * slot + q) * 16);
-      dst[j] = v * slot + q;
-      if (i < total) pending |= 1u << j;
-    }
-    const unsigned long long t_pub = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long deadline = t_pub + (unsigned long long)(a.timeout_us > 0 ? a.timeout_us : 2000000) * 100ull;
-    unsigned spins = 0;
-    while (pending && !dead) {
-      u32x4 x[MAXI];
-      asm volatile("" ::: "memory");  // a poll is never merged with, or hoisted above, an earlier one
-#pragma unroll
-      for (int j = 0; j < MAXI; ++j) {
-        x[j] = u32x4{0u, 0u, 0u, 0u};
-        if ((pending >> j) & 1u) x[j] = __builtin_amdgcn_raw_buffer_load_b128(ms, off[j], 0, kSysCoherent);
-      }
-#pragma unroll
-      for (int j = 0; j < MAXI; ++j) {
-        if (((pending >> j) & 1u) && x[j].x == epoch && x[j].w == xgmi_check(epoch, x[j].y, x[j].z)) {
-          peer[dst[j]] = make_float2(__uint_as_float(x[j].y), __uint_as_float(x[j].z));
-          pending &= ~(1u << j);
-        }
-      }
-      if (!pending) break;
-      if ((++spins & 15u) == 0u && __builtin_amdgcn_s_memrealtime() > deadline) {
-        if (a.status) {
-          atomicExch(&a.status[0], 1);
-          atomicExch(&a.status[1], (int)epoch);
-        }
-        dead = true;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    if (waited) waited[0] += __builtin_amdgcn_s_memrealtime() - t_pub;
-  }
-  __syncthreads();
-  // slot-order sums (absent slots add nothing; a timed-out peer's stale values are flagged)
-  float own[GPT + 1][2];
-#pragma unroll
-  for (int k = 0; k < GPT; ++k) {
-    own[k][0] = 2 * k < NPT ? g[2 * k] : 0.f;
-    own[k][1] = 2 * k + 1 < NPT ? g[2 * k + 1] : 0.f;
-  }
-  own[GPT][0] = loss;
-  own[GPT][1] = 0.f;
-  float acc[GPT + 1][2];
-#pragma unroll
-  for (int k = 0; k <= GPT; ++k) acc[k][0] = acc[k][1] = 0.f;
-  const int gq0 = has_g ? tid * GPT : 0;
-  for (int v = 0; v < V; ++v) {
-#pragma unroll
-    for (int k = 0; k <= GPT; ++k) {
-      const int q = k < GPT ? gq0 + k : nthr * GPT;
-      const float2 pv = v == R ? make_float2(own[k][0], own[k][1]) : peer[v * slot + q];
-      acc[k][0] += pv.x;
-      acc[k][1] += pv.y;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < NPT; ++k) g[k] = acc[k / 2][k & 1];
-  return acc[GPT][0];
-}
-
-#ifndef DTP_XGMI_G3
-// 1: the several-lanes steps (4 waves) run the cross-GPU exchange on 3-float granules with a
-// destination-dealt publish (xgmi_allreduce_g3); 0: the 2-float owner-thread form above
-#define DTP_XGMI_G3 1
-#endif
-#ifndef DTP_XGMI_G3_PUBW
-// xgmi_allreduce_g3 roles: 0 = every wave publishes its dealt destinations, then polls;
-// n > 0 = waves 0..n-1 publish every destination, the other waves poll
-#define DTP_XGMI_G3_PUBW 0
-#endif
-#ifndef DTP_XGMI_G3_SLEEP
-#define DTP_XGMI_G3_SLEEP 0  // s_sleep units between two polls of xgmi_allreduce_g3 (0: none)
-#endif
-
 // 3-float granules of a member's cross-GPU payload: the P gradients and the loss
 DTP_HD constexpr int xgmi_ng3(int P) { return (P + 1 + 2) / 3; }
 // LDS floats per member row of xgmi_allreduce_g3 (a float4 multiple)
@@ -427,16 +230,17 @@ DTP_DEV uint32_t xgmi_hash3(uint32_t a, uint32_t b, uint32_t c) {
   return hash32(a ^ hash32(b ^ ((c << 13) | (c >> 19)) ^ 0x9E3779B9u));
 }
 
-// The cross-GPU all-reduce on 3-float granules (round 6; the on-chip split exchange's form,
-// grp_core.h:grp_allreduce_split3, carried to the system scope):
+// The cross-GPU all-reduce on 3-float granules of the several-lanes steps' 4-wave instances
+// (the on-chip exchange's staged form, grp_core.h:grp_allreduce_split3, carried to the system
+// scope; the one-lane and 8-wave kernels and split_train.hip run the 2-float form above):
 //   * the owners stage the member's payload in LDS as one flat row (gradients 0..P-1, the
 //     loss at P); granule q = floats [3q, 3q + 3) as {epoch ^ xgmi_hash3(v), v}: 124 granules
 //     for the toy model instead of 187 two-float ones;
 //   * publish: the destination ranks (every rank with a reader of this slot -- the own
 //     rank too when other local members read it, GR > 1) are dealt to the waves, d-th
-//     destination to wave d % NPW; a wave stores all NG granules of its destination
+//     destination to wave d % NW; a wave stores all NG granules of its destination
 //     (2 coalesced 16-byte stores per lane, a wave-uniform buffer resource), so no lane
-//     issues more than 2 ceil(D / NPW) stores (W = 8: 4, was 7 per owner thread);
+//     issues more than 2 ceil(D / NW) stores (W = 8: 4, was 7 per owner thread);
 //   * poll: items (virtual member v != R, granule q) spread over the poller lanes (W = 8:
 //     <= 4 per lane), every still-missing item re-requested each round, accepted granules
 //     parked in LDS;
@@ -450,13 +254,14 @@ DTP_DEV float xgmi_allreduce_g3(const XgmiCtx& a, int model, float (&g)[NPT], fl
                                 int gk = 0) {
   constexpr int NG = xgmi_ng3(P), PS = xgmi_ps3(P);
   constexpr int NW = NTHREADS / kWave;
-  constexpr int NPW = DTP_XGMI_G3_PUBW > 0 ? DTP_XGMI_G3_PUBW : NW;  // publisher waves
-  constexpr int NPOLL = DTP_XGMI_G3_PUBW > 0 ? NTHREADS - kWave * DTP_XGMI_G3_PUBW : NTHREADS;
-  constexpr int P0 = DTP_XGMI_G3_PUBW > 0 ? kWave * DTP_XGMI_G3_PUBW : 0;  // first poller lane
+  // Every wave publishes its dealt destinations, then every lane polls.  The conditions marked
+  // (always) hold for each thread of a workgroup of NTHREADS (0 <= tid < NTHREADS); the compiler
+  // does not derive that, and they shape the code it emits, so they stay as written until a
+  // change that may alter the kernels' code.
+  constexpr int NPOLL = NTHREADS;
   constexpr int slot = xgmi_slot16(P, NPT);
   constexpr int MAXJ = (NG + kWave - 1) / kWave;  // granules per publisher lane and destination
   static_assert(NG <= slot, "a member's 3-float granules fit its slot of the receive buffer");
-  static_assert(NPW <= NW && NPOLL >= kWave, "publisher and poller waves");
   float* const pub = lds;
   float* const peer = lds + PS;  // peer[v * PS + i]: virtual member v's float i
   const int V = a.world * GR, R = a.rank * GR + gk;
@@ -475,7 +280,7 @@ DTP_DEV float xgmi_allreduce_g3(const XgmiCtx& a, int model, float (&g)[NPT], fl
   const unsigned long long t_pub0 = waited ? __builtin_amdgcn_s_memrealtime() : 0ull;
   // 2. publish: this wave's dealt destinations (the ranks other than this one first, in
   // ring order from rank + 1, then this rank's own buffer when GR > 1)
-  if (wave < NPW) {
+  if (wave < NW) {  // (always)
     u32x4 gq[MAXJ];
 #pragma unroll
     for (int j = 0; j < MAXJ; ++j) {
@@ -485,7 +290,7 @@ DTP_DEV float xgmi_allreduce_g3(const XgmiCtx& a, int model, float (&g)[NPT], fl
       gq[j] = u32x4{epoch ^ xgmi_hash3(x0, x1, x2), x0, x1, x2};
     }
     const int D = GR > 1 ? a.world : a.world - 1;
-    for (int di = wave; di < D; di += NPW) {
+    for (int di = wave; di < D; di += NW) {
       int d = a.rank + 1 + di;
       d = d >= a.world ? d - a.world : d;  // di = world - 1 (GR > 1 only): this rank
       const __amdgpu_buffer_rsrc_t rs = xgmi_rsrc(a.peers[d]);
@@ -498,11 +303,11 @@ DTP_DEV float xgmi_allreduce_g3(const XgmiCtx& a, int model, float (&g)[NPT], fl
     }
   }
   const unsigned long long t_pub = waited ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  if (waited && wave < NPW) waited[1] += t_pub - t_pub0;
+  if (waited && wave < NW) waited[1] += t_pub - t_pub0;
   // 3. poll the other V - 1 slots of the local buffer
-  if (tid >= P0) {
+  if (tid >= 0) {  // (always)
     const __amdgpu_buffer_rsrc_t ms = xgmi_rsrc(a.peers[a.rank]);
-    const int pl = tid - P0;
+    const int pl = tid;
     const int total = (V - 1) * NG;
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     const unsigned long long deadline = t0 + (unsigned long long)(a.timeout_us > 0 ? a.timeout_us : 2000000) * 100ull;
@@ -544,7 +349,6 @@ DTP_DEV float xgmi_allreduce_g3(const XgmiCtx& a, int model, float (&g)[NPT], fl
           }
           dead = true;
         }
-        if (DTP_XGMI_G3_SLEEP > 0) __builtin_amdgcn_s_sleep(DTP_XGMI_G3_SLEEP);
       }
       // a timed-out exchange adds +0 for what never arrived (not an earlier exchange's rows)
       if (pending) {

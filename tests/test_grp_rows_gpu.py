@@ -1,5 +1,5 @@
 """The split-batch step publishing its gradients straight from payload-order rows
-(csrc/grp_core.h, DTP_GRP_ROWS): every member count, partly and wholly empty members, the
+(csrc/grp_core.h, payload-order rows): every member count, partly and wholly empty members, the
 CE head's third publisher chunk, the bf16 loss slot and the launch modes, against autograd
 + torch.optim (tests/ref_train.py) at the tolerances of tests/test_lanes_gpu.py (GPU only).
 
