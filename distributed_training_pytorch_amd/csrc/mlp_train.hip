@@ -574,6 +574,13 @@ struct LaneSmem {
   alignas(16) float2 gx[GRP ? GX2 : 2];
 };
 
+// waves per SIMD the register budget is set for: 2 on the 4-wave split-batch instances (256
+// VGPRs, 169 used; they still run one wave per SIMD), so that the dW tiles' MFMAs write
+// VGPRs -- with the 512 registers of one wave per SIMD the compiler puts their results in
+// AGPRs and copies every tile out (8 v_accvgpr_read and the s_nop in front of them per tile)
+template <int NW, bool GRP>
+constexpr int lanes_wpe = (GRP && NW == 4) ? 2 : NW / 4;
+
 // NW waves per workgroup (4: one per SIMD; 8: two per SIMD, for batches of 256 / L < B <= 512 / L)
 // GRP: the batch split over a.groups workgroups per model (grp_core.h): member k of model m
 // is block m + 8 k (the members of a model share an XCD under round-robin dispatch), runs
@@ -584,7 +591,8 @@ struct LaneSmem {
 // SGD (momentum, weight decay), local or with the in-kernel xGMI exchange.
 // GRC > 0: the member count of the split-batch step as a constant (a.groups == GRC).
 template <class S, int L, int MODE, bool PROF = false, int NW = 4, bool GRP = false, bool CE = false, int GRC = 0>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(NW / 4, NW / 4)))
+__global__ __launch_bounds__(64 * NW)
+__attribute__((amdgpu_waves_per_eu(lanes_wpe<NW, GRP>, lanes_wpe<NW, GRP>)))
 void mlp_train_lanes_kernel(DtpTrainArgs a) {
   using SC = Scal<S>;
   using C = LaneCfg<S, L>;
@@ -688,6 +696,11 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   if (htab) adam_tab_load<kAdamTab / NTH, NTH>(a, t0, 0, tid, tabv);
   int epoch = t0 / smp.steps_per_epoch;
   int bi = t0 - epoch * smp.steps_per_epoch;
+  // the sample after next: its permutation word is loaded a whole step before the gather
+  // that consumes it, so the word travels raw with `fok` (is this lane's batch position
+  // inside that batch?) and the -1 of a position past a ragged batch is formed at the
+  // gather -- nothing waits for the load at the end of the step that issued it
+  bool fok = true;
   auto fast_index = [&](int ep_, int b_) -> int {
     const int start = b_ * smp.batch;
     const int size = min(smp.batch, smp.num_samples - start);
@@ -695,7 +708,8 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     q = q >= smp.n ? q - smp.n : q;
     q = q < smp.n ? q : smp.n - 1;
     const int di = table_epoch(smp, ep_)[q];
-    return bk < size ? di : -1;
+    fok = bk < size;
+    return di;
   };
   auto roll = [&](int& ep_, int& b_) {
     const bool r_ = ++b_ == smp.steps_per_epoch;
@@ -704,6 +718,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   };
   int e2 = epoch, b2 = bi;
   const int fidx0 = fast_index(epoch, bi);
+  const bool fok0 = fok;
   roll(e2, b2);
   int fidx = fast_index(e2, b2);
   unsigned xepoch = kXgmi ? a.epoch[model] : (GRP ? a.grp_epoch[model] : 0u);  // GRP + xGMI: the xGMI epochs
@@ -765,7 +780,8 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   const int lend = a.loss_log ? a.loss_log_cap * a.n_models : a.n_models;
   int loff = lslot * a.n_models + model;
   int refill = kAdamTab;
-  auto fast_gather = [&](int di, float (&x)[S::IN], float (&y)[S::OUT]) {
+  auto fast_gather = [&](int di, bool ok, float (&x)[S::IN], float (&y)[S::OUT]) {
+    di = ok ? di : -1;
     const bool v = di >= 0;
     di = (unsigned)di < (unsigned)smp.n ? di : 0;
     static_for<0, S::IN>([&](auto IC) {
@@ -781,7 +797,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     return v;
   };
   float nx[S::IN], ny[S::OUT];
-  bool nvalid = fast_gather(fidx0, nx, ny);
+  bool nvalid = fast_gather(fidx0, fok0, nx, ny);
   auto fill_adam = [&](int base) {
     const int n = min(kAdamTab, a.n_steps - base);
     if (htab) {
@@ -818,13 +834,23 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     }
   };
   const bool p0 = part == 0;
+  // 1 / (batch size [x OUT]): a batch is full or the epoch's ragged last one, so the two
+  // reciprocals are divided once per launch and a step selects by its batch index
+  auto inv_of = [&](int b_) {
+    const int bsz = min(smp.batch, smp.num_samples - b_ * smp.batch);
+    return CE ? 1.f / (float)bsz : 1.f / (float)(bsz * S::OUT);
+  };
+  const int blast = smp.steps_per_epoch - 1;
+  // (pinned in registers by an empty asm: otherwise the select of two quotients is folded
+  // into the quotient of a select, back inside the loop)
+  float inv_full = inv_of(0), inv_last = inv_of(blast);
+  asm volatile("" : "+v"(inv_full), "+v"(inv_last));
   __syncthreads();
   stamp_launch(29);
 
   for (int it = 0; it < a.n_steps; ++it) {
     DTP_STAMP(0);
-    const int bsz = min(smp.batch, smp.num_samples - bi * smp.batch);
-    const float inv = CE ? 1.f / (float)bsz : 1.f / (float)(bsz * S::OUT);
+    const float inv = bi == blast ? inv_last : inv_full;
     f32x4 acc[NT];
 #pragma unroll
     for (int q = 0; q < NT; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1034,7 +1060,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       if constexpr (!kDiet) {
         if (a.loss_log && ++lslot == a.loss_log_cap) lslot = 0;
       }
-      nvalid = fast_gather(fidx, nx, ny);
+      nvalid = fast_gather(fidx, fok, nx, ny);
       roll(e2, b2);
       fidx = fast_index(e2, b2);
     };
@@ -1116,10 +1142,15 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       if ((kAdam || ltab) && --refill == 0 && it + 1 < a.n_steps) {
         refill = kAdamTab;
         fill_adam(it + 1);
+        // the refill's predicated table loads are all consumed here, once per kAdamTab steps:
+        // none counts as outstanding where this path rejoins the step, whose end would
+        // otherwise wait for every load in flight, the next-but-one sample's index included
+        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
         __syncthreads();
       }
     } else if ((kAdam || ltab) && (it + 1) % kAdamTab == 0 && it + 1 < a.n_steps) {
       fill_adam(it + 1);
+      __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), as above
       __syncthreads();
     }
     DTP_STAMP(7);
