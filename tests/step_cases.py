@@ -1,8 +1,9 @@
 """The fused step's gradient, read out exactly through the optimizer state, against fp64
 autograd -- one cell per kernel instance the dispatcher of ``csrc/mlp_train.hip`` can pick.
 
-Shared by ``tests/test_step_matrix_gpu.py`` and ``tests/test_step_matrix_cpu.py``; CPU-only
-code except :func:`run_cell`, which drives a ``FusedTrainer`` on whatever device it is given.
+Shared by ``tests/test_step_matrix_gpu.py``, ``tests/test_xgmi_matrix_gpu.py`` and
+``tests/test_step_matrix_cpu.py``; CPU-only code except :func:`run_cell` and :func:`run_cell_rank`,
+which drive a ``FusedTrainer`` on whatever device they are given.
 
 **Read-out.**  ``adam_update`` forms ``m = fmaf(1 - b1, g - m, m)`` and ``sgd_update`` (momentum
 != 0, no weight decay) ``buf = g`` on the first step, ``fmaf(buf, mom, g)`` later
@@ -54,18 +55,32 @@ the step, ``v1 = (1 - b2) m^2`` and ``dp = -lr m / (sqrt(v1 / bc2) + eps)``, ``b
 asserted are the sign, ``|dp| <= lr c (1 + 1e-3)`` with ``c = sqrt(bc2 / (1 - b2))`` (1 at step 0,
 where this is ``|dp| <= lr (1 + 1e-3)``; later steps of a freshly zeroed ``v`` are bias-corrected
 by more than ``v`` holds) and the formula itself to rtol 1e-5.
+
+**Several ranks** (``XGMI_CELLS``, ``tests/test_xgmi_matrix_gpu.py``).  Under
+``DTP_MODE_XGMI_ADAM`` / ``_SGD`` every rank's step sums the W x members gradients in slot order
+inside the kernel and the optimizer takes that sum times ``grad_scale = 1 / W``; every rank
+zeroes its moments at the same step (:func:`step_gradient_world`), and the read-out is that
+product -- the same bits on every rank, which is asserted.  Reference: the mean over the ranks
+of fp64 autograd on each rank's ``step_indices(t)`` (loss: the mean of the ranks' mean losses);
+``Y``: fp32 autograd per rank, summed in fp32 in rank order, times fp32 ``1 / W``; the CE margin
+and the own margin are the means of the ranks' absolute margins (a bound of the mean's error),
+``sum_chain`` counting the V slot additions.  Bounds and constants are those above.  The
+conditions on the inputs are checked on the CPU along ``ref_train.torch_train``'s trajectory
+(one geometry per rank; ``tests/test_step_matrix_cpu.py``); the seeds below were the first
+tried for these cells and met them in every one, so no others were.  No cell of several ranks
+needed ``own_margin``: the largest E / bound of the run kept in ``profiles/xgmi_matrix/`` is 0.49.
 """
 from __future__ import annotations
 
 import json
 import math
 import sys
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import NamedTuple
 
 import torch
 
-from distributed_training_pytorch_amd.data.sampler import SamplerGeometry
+from distributed_training_pytorch_amd.data.sampler import EpochIndexStream, SamplerGeometry
 from distributed_training_pytorch_amd.data.toy_data import ToyData
 from distributed_training_pytorch_amd.engine.fused_trainer import EngineConfig, FusedTrainer
 from distributed_training_pytorch_amd.ops.mlp import MlpSpec, mlp_forward_ref, mlp_forward_ref_bf16, unflatten
@@ -101,10 +116,13 @@ class Cell:
     n: int = 512
     env: tuple = ()            # (("DTP_LANES", "2x8"),): a forced instance, run in a child process
     own_margin: bool = False   # the fp32 bound plus the running-error margin (fp32_margin)
+    world: int = 1             # ranks (> 1: the xGMI modes, XGMI_CELLS below; all ranks share one GPU)
 
     @property
     def id(self) -> str:
         s = f"{self.shape}-{self.opt}-{self.loss}-{self.prec}-b{self.batch}-g{self.groups}"
+        if self.world != 1:
+            s = f"w{self.world}-" + s
         if not self.cache:
             s += "-nocache"
         if self.n != 512:
@@ -210,14 +228,105 @@ FORCED = [
 ]
 
 ALL_CELLS = CELLS + FORCED
-BY_ID = {c.id: c for c in ALL_CELLS}
-assert len(BY_ID) == len(ALL_CELLS), "duplicate cell ids"
+
+
+# ---- the xGMI modes: W ranks, every rank's step summed inside the kernel through one of the
+# exchanges of csrc/xgmi_core.h.  xgmi_allreduce_slots (2-float granules, a pending-mask bit
+# r (GPT + 1) + k per slot r and granule k of a thread): the one-lane kernels and the 8-wave
+# lanes instances.  xgmi_allreduce_g3 (3-float granules staged in LDS): the 4-wave lanes and
+# split-batch instances, over V = W x members slots; its poll loop is one of four bodies picked
+# by pi = ceil((V - 1) NG / 256), NG = ceil((P + 1) / 3) = 124 (T), 135 (C4), 261 (H15), 101 (N3):
+# PI = 1, 2, min(4, MAXI), MAXI = ceil(7 NG / 256); its publish deals destination rank di to wave
+# di % 4 (D = W - 1 destinations, W with members), so a wave takes a second one from W = 6.
+# n = 512 over W ranks: 256 / 171 / 103 / 64 samples per rank, the list padded to 513 (W = 3) and
+# 515 (W = 5) so that the last ranks' shares wrap to the head of the permutation.
+def _w(world, *cells):
+    return [replace(c, world=world) for c in cells]
+
+
+XGMI_CELLS = (
+    # ---- W = 2, one lane (batch 200 of 256 per rank; last batch 56): slots, V = 2
+    _w(2, _one("T", "adam", "mse", 200, "fast"), _one("N3", "adam", "mse", 200, "fast"),      # NPT 2, 1
+       _one("H15", "adam", "mse", 200, "fast"), _one("C4", "adam", "mse", 200, "fast"),      # NPT 4, 2
+       _one("T", "sgd", "mse", 200, "generic"), _one("C4", "adam", "ce", 200, "generic"),
+       _one("C4", "sgd", "ce", 200, "generic"), _one("T", "adam", "mse", 200, "fast", prec="bf16"),
+       # the remaining one-lane instances of train_fn's two xGMI modes (XGMI_INSTANCES)
+       _one("T", "adam", "mse", 200, "generic", cache=False), _one("N3", "adam", "mse", 200, "generic", cache=False),
+       _one("H15", "adam", "mse", 200, "generic", cache=False), _one("C4", "adam", "mse", 200, "generic", cache=False),
+       _one("H15", "sgd", "mse", 200, "generic"), _one("C4", "sgd", "mse", 200, "generic"),
+       _one("T", "adam", "mse", 200, "generic", prec="bf16", cache=False), _one("T", "sgd", "mse", 200, "generic", prec="bf16"),
+       _one("C4", "adam", "mse", 200, "fast", prec="bf16"), _one("C4", "adam", "mse", 200, "generic", prec="bf16", cache=False),
+       _one("C4", "sgd", "mse", 200, "generic", prec="bf16"), _one("C4", "adam", "ce", 200, "generic", prec="bf16"),
+       _one("C4", "sgd", "ce", 200, "generic", prec="bf16"),
+       # split-batch: V = 2 x members slots of g3
+       _grp("T", "adam", "mse", 256, 4),                                    # V = 8, pi = 4
+       _grp("T", "sgd", "mse", 130, 3),                                     # V = 6, the third member: 2 samples
+       _grp("C4", "adam", "ce", 128, 2), _grp("C4", "sgd", "ce", 128, 2),   # V = 4, pi = 2
+       _grp("T", "adam", "mse", 256, 4, prec="bf16"))
+    # ---- W = 3 (171 per rank): 2 lanes at batch 100 (last batch 71), g3 with V = 3
+    + _w(3, _lanes("T", "adam", "mse", 100, 2), _lanes("T", "sgd", "mse", 100, 2), _lanes("C4", "sgd", "ce", 100, 2),
+         _lanes("H15", "adam", "mse", 100, 2),                               # pi = 3: the PI = 4 body
+         _lanes("N3", "adam", "mse", 100, 2), _lanes("C4", "adam", "mse", 100, 2), _lanes("C4", "adam", "ce", 100, 2),
+         _lanes("T", "adam", "mse", 100, 2, prec="bf16"),
+         _grp("T", "adam", "mse", 128, 2),                                   # V = 6, pi = 3; last batch 43: a member empty
+         _one("N3", "sgd", "mse", 171, "generic"))                           # no N3 SGD lanes instance: slots, NPT 1
+    # ---- W = 5 (103 per rank)
+    + _w(5, _lanes("H15", "adam", "mse", 70, 2),                             # pi = 5: the MAXI = 8 body
+         _lanes("T", "adam", "mse", 50, 4), _lanes("C4", "adam", "ce", 50, 4), _lanes("T", "adam", "mse", 50, 4, prec="bf16"),
+         _lanes("N3", "adam", "mse", 50, 4))
+    # ---- W = 8 (64 per rank): 4 lanes at batch 50 (last batch 14); publish round two (D = 7)
+    + _w(8, _lanes("T", "adam", "mse", 50, 4),                               # pi = 4
+         _lanes("H15", "adam", "mse", 50, 4),                                # pi = 8
+         _lanes("C4", "adam", "mse", 50, 4), _lanes("C4", "sgd", "ce", 50, 4), _lanes("T", "sgd", "mse", 50, 4),
+         _lanes("T", "adam", "mse", 50, 4, prec="bf16"), _lanes("N3", "adam", "mse", 50, 4),
+         # one lane at n = 2048 (256 per rank; above kLaneData, so neither lanes nor split-batch): slots r <= 7
+         _one("T", "adam", "mse", 256, "fast", n=2048), _one("H15", "adam", "mse", 200, "fast", n=2048),  # NPT 4, GPT 2
+         _one("T", "sgd", "mse", 200, "generic", n=2048))
+)
+# forced 8-wave lanes instances (slots at 512 threads): one spawn per value
+XGMI_FORCED = _w(2, Cell("T", "adam", "mse", 128, (4, 8, 1), "lanes", groups="auto", env=(("DTP_LANES", "4x8"),)),
+                 Cell("T", "adam", "mse", 256, (2, 8, 1), "lanes", groups="auto", env=(("DTP_LANES", "2x8"),)))
+ALL_XGMI = XGMI_CELLS + XGMI_FORCED
+# the W = 8 check of launch="graph" against launch="persistent" (tests/test_xgmi_matrix_gpu.py)
+XGMI_GRAPH_CELL = XGMI_CELLS[[c.id for c in XGMI_CELLS].index("w8-T-adam-mse-fp32-b50-goff")]
+
+BY_ID = {c.id: c for c in ALL_CELLS + ALL_XGMI}
+assert len(BY_ID) == len(ALL_CELLS) + len(ALL_XGMI), "duplicate cell ids"
+
+
+def _xgmi_instances():
+    """What train_fn / lanes_inst / grp_inst instantiate for DTP_MODE_XGMI_ADAM and
+    DTP_MODE_XGMI_SGD, in the form of :func:`_instances` -- written out from those functions,
+    NOT derived from XGMI_CELLS."""
+    out = []
+    # train_fn: launch_mode<S, XGMI_ADAM, true> (FAST), launch_mode<S, XGMI_ADAM>, launch_mode<S, XGMI_SGD>
+    for prec, shapes in (("fp32", ("T", "N3", "C4", "H15")), ("bf16", ("T", "C4"))):
+        for s in shapes:
+            out += [(s, 1, 4, "mse", "adam", prec, "fast"), (s, 1, 4, "mse", "adam", prec, "generic"),
+                    (s, 1, 4, "mse", "sgd", prec, "generic")]
+            if s == "C4":
+                out += [(s, 1, 4, "ce", "adam", prec, "generic"), (s, 1, 4, "ce", "sgd", prec, "generic")]
+    # lanes_modes: every lanes instance has its xGMI twin
+    for L in (2, 4):
+        out += [(s, L, 4, "mse", "adam", "fp32", "lanes") for s in ("T", "N3", "C4", "H15")]
+        out += [("T", L, 4, "mse", "sgd", "fp32", "lanes"), ("C4", L, 4, "ce", "adam", "fp32", "lanes"),
+                ("C4", L, 4, "ce", "sgd", "fp32", "lanes"), ("T", L, 4, "mse", "adam", "bf16", "lanes"),
+                ("T", L, 8, "mse", "adam", "fp32", "lanes")]
+    # grp_inst: one instance per family (the member count is read at run time); DTP_GRP_NW=8 is
+    # one-rank only
+    out += [("T", 4, 4, "mse", "adam", "fp32", "grp"), ("T", 4, 4, "mse", "sgd", "fp32", "grp"),
+            ("T", 4, 4, "mse", "adam", "bf16", "grp"), ("C4", 4, 4, "ce", "adam", "fp32", "grp"),
+            ("C4", 4, 4, "ce", "sgd", "fp32", "grp")]
+    return out
+
+
+XGMI_INSTANCES = _xgmi_instances()
 
 
 def _instances():
     """What train_fn / lanes_inst / grp_inst instantiate for the local optimizer modes, as
     (shape, lanes, waves, loss, optimizer, precision, kind) -- written out from those
-    functions, NOT derived from CELLS.  (MODE_GRAD and the xGMI modes: other tests.)"""
+    functions, NOT derived from CELLS.  (The xGMI modes: XGMI_INSTANCES; MODE_GRAD: other tests.)"""
     out = []
     # train_fn<Stage<...>>: every DTP_TRAIN_SHAPES shape in fp32, DTP_TRAIN_BF16_SHAPES in bf16;
     # FAST = Adam + MSE; the generic kernel takes the loss at run time (CE: the 4-class head)
@@ -264,8 +373,14 @@ def cell_init(cell: Cell):
     return [torch.randn(cell.spec.P, generator=g) * 0.4 for _ in range(N_MODELS)]
 
 
-def cell_geom(cell: Cell) -> SamplerGeometry:
-    return SamplerGeometry(n=cell.n, batch=cell.batch, seed=SAMPLER_SEED)
+def cell_geom(cell: Cell, rank: int = 0) -> SamplerGeometry:
+    return SamplerGeometry(n=cell.n, world=cell.world, rank=rank, batch=cell.batch, seed=SAMPLER_SEED)
+
+
+def cell_indices(cell: Cell, t: int) -> list[list[int]]:
+    """Every rank's batch of step t, in rank order (the engine's default order: torch's
+    DistributedSampler, the permutation padded by repeating from its start)."""
+    return [EpochIndexStream(cell_geom(cell, r)).indices(t) for r in range(cell.world)]
 
 
 def readout_steps(cell: Cell) -> list[int]:
@@ -274,11 +389,11 @@ def readout_steps(cell: Cell) -> list[int]:
     return sorted({0, spe - 1, spe})
 
 
-def make_trainer(cell: Cell, device, prec: str | None = None) -> FusedTrainer:
+def make_trainer(cell: Cell, device, prec: str | None = None, rank: int = 0, **cfg) -> FusedTrainer:
     X, Y = cell_data(cell)
-    ecfg = EngineConfig(steps_per_launch=STEPS_PER_LAUNCH, loss=cell.loss, groups=cell.groups,
-                        cache_data=cell.cache, precision=prec or cell.prec)
-    return FusedTrainer(cell.spec, N_MODELS, X.to(device), Y.to(device), cell_geom(cell),
+    ecfg = EngineConfig(**{"steps_per_launch": STEPS_PER_LAUNCH, "loss": cell.loss, "groups": cell.groups,
+                           "cache_data": cell.cache, "precision": prec or cell.prec, **cfg})
+    return FusedTrainer(cell.spec, N_MODELS, X.to(device), Y.to(device), cell_geom(cell, rank),
                         ADAM if cell.opt == "adam" else SGD, ecfg, init_params=[p.to(device) for p in cell_init(cell)])
 
 
@@ -301,6 +416,31 @@ def step_gradient(tr: FusedTrainer) -> StepGradient:
     tr.m.zero_()
     tr.v.zero_()
     t = tr.t
+    tr.train(1)
+    tr.synchronize()
+    assert tr.t == t + 1
+    return StepGradient(t, p0, tr.m.detach().cpu().clone(), tr.losses(t, t + 1)[0].clone(),
+                        tr.params.detach().cpu().clone())
+
+
+def step_gradient_world(tr: FusedTrainer) -> StepGradient:
+    """:func:`step_gradient` on every rank of a W-rank engine at the same step.  Under the
+    xGMI modes the optimizer takes the slot-order fp32 sum of the members' gradients times
+    ``grad_scale = 1 / W`` (``mlp_train.hip``: ``g[k] * a.hp.grad_scale``), so with zeroed
+    moments ``tr.m[i]`` is that product bit for bit -- the same bits on every rank.  Every rank
+    calls this at the same ``tr.t``; a process-group barrier lets the ranks enter the launch
+    together (the exchange's wait is bounded by ``xgmi_timeout_us``)."""
+    import torch.distributed as dist
+
+    o = tr.optim
+    assert (o.name == "adam" and o.betas[0] == 0.0) or (o.name == "sgd" and o.momentum != 0.0), o
+    assert o.weight_decay == 0.0 and not o.clips and tr.comm == "xgmi"
+    tr.synchronize()
+    p0 = tr.params.detach().cpu().clone()
+    tr.m.zero_()
+    tr.v.zero_()
+    t = tr.t
+    dist.barrier()
     tr.train(1)
     tr.synchronize()
     assert tr.t == t + 1
@@ -332,8 +472,22 @@ def rel(a, b) -> float:
     return abs(float(a) - float(b)) / abs(float(b))
 
 
+def per_tensor(spec, bound, g64) -> dict:
+    """An absolute per-element bound [P] as the metric's: its largest element over max|g64|, per tensor."""
+    return {n: (b.max() / r.abs().max()).item()
+            for n, b, r in zip(tensor_names(spec), unflatten(bound, spec), unflatten(g64, spec))}
+
+
 def ce_margin(spec, p, x, y, g64) -> tuple[dict, float]:
     """The cross-entropy cells' margin (module docstring): per tensor, and for the loss."""
+    bound, lbound = ce_margin_abs(spec, p, x, y)
+    l64 = torch.nn.functional.cross_entropy(mlp_forward_ref(p.double(), spec, x.double()), y.view(-1).long())
+    return per_tensor(spec, bound, g64), (lbound / l64.abs()).item()
+
+
+def ce_margin_abs(spec, p, x, y) -> tuple[torch.Tensor, torch.Tensor]:
+    """:func:`ce_margin` as absolute bounds: per gradient element [P], and of the loss.  (Several
+    ranks: the mean of the ranks' bounds bounds the mean of their gradients.)"""
     p64, x64 = p.double(), x.double()
     out = mlp_forward_ref(p64, spec, x64)                            # [B, C]
     A = torch.func.jacrev(lambda q: mlp_forward_ref(q, spec, x64))(p64)  # [B, C, P]
@@ -344,13 +498,10 @@ def ce_margin(spec, p, x, y, g64) -> tuple[dict, float]:
     delta = eps + eps.max(1, keepdim=True).values + 8 * U
     prob = torch.softmax(out, 1)
     bound = torch.einsum("sjk,sj->k", A.abs(), prob * delta) / B
-    names = tensor_names(spec)
-    m = {n: (b.max() / r.abs().max()).item() for n, b, r in zip(names, unflatten(bound, spec), unflatten(g64, spec))}
     lse = torch.logsumexp(out, 1)
     logse = (lse - mx.view(-1)).abs()
     per = eps.max(1).values + 3 * U + 3 * U * logse + U * (mx.view(-1).abs() + lse.abs())
-    l64 = torch.nn.functional.cross_entropy(out, y.view(-1).long())
-    return m, (per.mean() / l64.abs()).item()
+    return bound, per.mean()
 
 
 def sum_chain(cell: Cell, bsz: int) -> int:
@@ -359,10 +510,11 @@ def sum_chain(cell: Cell, bsz: int) -> int:
     256-sample chunk (``bk = gk (NW G) + wave G + ws`` with ``G = 64 / L`` in
     ``mlp_train_lanes_kernel``; one lane: ``c0 + tid`` over the chunks of ``mlp_train_kernel``)
     -- then the waves' tiles are summed, then the members', plus the two merges of the split
-    accumulators (``a0 += a1``, ``wave_outer_acc``)."""
+    accumulators (``a0 += a1``, ``wave_outer_acc``).  Several ranks: the members' sum is the
+    exchange's, over its V = world x members slots."""
     lanes, waves, groups = cell.expect
     chunks = -(-bsz // 256) if lanes == 1 else 1
-    return (64 // lanes) * chunks + waves + groups + 2
+    return (64 // lanes) * chunks + waves + cell.world * groups + 2
 
 
 LAMBDA = 6.0  # |sum c_i d_i| <= LAMBDA u sqrt(sum c_i^2) fails with probability <= 2 exp(-LAMBDA^2 / 2) = 3e-8
@@ -392,6 +544,13 @@ def fp32_margin(spec, p, x, y, n_sum: int) -> dict:
     cancellation, as any fp32 evaluation's error does -- and there fp32 autograd's own error
     ``Y``, a single draw of this distribution, says little (seen down to 2e-9, a hundredth of
     ``u``, beside kernel errors of 13 u).  Not modelled: a pre-activation within its error of 0."""
+    g64, _ = autograd_gradient(spec, p, x, y, "mse", torch.float64)
+    return per_tensor(spec, fp32_margin_abs(spec, p, x, y, n_sum), g64)
+
+
+def fp32_margin_abs(spec, p, x, y, n_sum: int) -> torch.Tensor:
+    """:func:`fp32_margin` as an absolute bound per gradient element [P].  (Several ranks: the
+    mean of the ranks' bounds bounds the mean of their gradients.)"""
     ps = [t.double() for t in unflatten(p.double(), spec)]
     NL, B = spec.n_layers, x.shape[0]
     x64, y64 = x.double(), y.double()
@@ -445,27 +604,45 @@ def fp32_margin(spec, p, x, y, n_sum: int) -> dict:
     g0 = step(eps0)
     g64, _ = autograd_gradient(spec, p, x, y, "mse", torch.float64)
     assert (g0 - g64).abs().max() <= 1e-12 * g64.abs().max(), "the written-out step is not the step"
-    bound = LAMBDA * var.sqrt()
-    return {n: (b.max() / r_.abs().max()).item() for n, b, r_ in zip(tensor_names(spec), unflatten(bound, spec),
-                                                                     unflatten(g64, spec))}
+    return LAMBDA * var.sqrt()
 
 
 def evaluate_step(cell: Cell, sg: StepGradient, indices: list[int], X, Y) -> tuple[list[dict], list[str]]:
-    """Records (one per model) and failures of one read-out against the references."""
+    """Records (one per model) and failures of one read-out against the references.
+
+    A cell of several ranks (``cell.world > 1``) takes one index list per rank, in rank order
+    (:func:`cell_indices`): the reference is the mean over the ranks of fp64 autograd on each
+    rank's batch (the loss: of the ranks' mean losses), the yardstick ``Y`` fp32 autograd per
+    rank summed in fp32 in rank order and multiplied by fp32 ``1 / W``, and a margin the mean of
+    the ranks' absolute margins -- a bound of the mean's error."""
     spec, recs, fails = cell.spec, [], []
-    idx = torch.tensor(indices, dtype=torch.long)
-    x, y = X[idx], Y[idx]
+    per_rank = indices if cell.world > 1 else [indices]
+    assert len(per_rank) == cell.world and all(len(ix) > 0 for ix in per_rank)
+    W = len(per_rank)
+    batches = [(X[torch.tensor(ix, dtype=torch.long)], Y[torch.tensor(ix, dtype=torch.long)]) for ix in per_rank]
+    sizes = [len(ix) for ix in per_rank]
     bf = cell.prec == "bf16"
+
+    def mean(dtype, forward=mlp_forward_ref):
+        g, lo = None, None
+        for x, y in batches:  # rank order
+            gr, lr = autograd_gradient(spec, p, x, y, cell.loss, dtype, forward)
+            g, lo = (gr, lr) if g is None else (g + gr, lo + lr)
+        if W > 1:
+            inv = torch.tensor(1.0 / W, dtype=dtype)
+            g, lo = g * inv, lo * inv
+        return g, lo
+
     for i in range(N_MODELS):
         p = sg.params_before[i]
-        g64, l64 = autograd_gradient(spec, p, x, y, cell.loss, torch.float64)
-        g32, l32 = autograd_gradient(spec, p, x, y, cell.loss, torch.float32)
+        g64, l64 = mean(torch.float64)
+        g32, l32 = mean(torch.float32)
         Yt, Yl = metric(spec, g32, g64), rel(l32, l64)
-        rec = {"cell": cell.id, "t": sg.t, "model": i, "bsz": len(indices), "Y": Yt, "Y_loss": Yl}
+        rec = {"cell": cell.id, "t": sg.t, "model": i, "bsz": sizes[0] if W == 1 else sizes, "Y": Yt, "Y_loss": Yl}
         big = max(t.abs().max().item() for t in unflatten(g64, spec))
         rec["min_tensor_max"] = min(t.abs().max().item() for t in unflatten(g64, spec)) / big
         if bf:
-            gb, lb = autograd_gradient(spec, p, x, y, cell.loss, torch.float64, mlp_forward_ref_bf16)
+            gb, lb = mean(torch.float64, mlp_forward_ref_bf16)
             rec["D"], rec["D_loss"] = metric(spec, gb, g64), rel(lb, l64)
             ref_g, ref_l = gb, lb
         else:
@@ -473,13 +650,16 @@ def evaluate_step(cell: Cell, sg: StepGradient, indices: list[int], X, Y) -> tup
             bound = {n: max(4 * v, 8 * U) for n, v in Yt.items()}
             lbound = max(4 * Yl, 8 * U)
             if cell.loss == "ce":
-                mt, ml = ce_margin(spec, p, x, y, g64)
+                ab = [ce_margin_abs(spec, p, x, y) for x, y in batches]
+                mt = per_tensor(spec, sum(b for b, _ in ab) / W, g64)
+                ml = (sum(m for _, m in ab) / W / l64.abs()).item()
                 rec["margin"], rec["margin_loss"] = mt, ml
                 bound = {n: bound[n] + mt[n] for n in bound}
                 lbound += ml
             if cell.own_margin:
                 assert cell.loss == "mse"
-                mt = fp32_margin(spec, p, x, y, sum_chain(cell, len(indices)))
+                mt = per_tensor(spec, sum(fp32_margin_abs(spec, p, x, y, sum_chain(cell, max(sizes)))
+                                          for x, y in batches) / W, g64)
                 rec["margin"] = mt
                 bound = {n: bound[n] + mt[n] for n in bound}
             rec["bound"], rec["bound_loss"] = bound, lbound
@@ -596,6 +776,116 @@ def run_cell(cell: Cell, device, expect_instance: bool = True) -> tuple[list[dic
         fails += check_bf16(cell, recs)
     # (the conditions on the inputs are checked on the CPU engine's trajectory,
     # tests/test_step_matrix_cpu.py: Y at a snapshot a rounding apart is another draw)
+    return recs, fails
+
+
+# ------------------------------------------------------------------------------ a cell of W ranks
+def _all_ranks(ok: bool) -> bool:
+    """True on every rank iff ``ok`` on every rank: the ranks leave a cell together, whatever
+    failed on one of them (no rank is left alone in a collective)."""
+    import torch.distributed as dist
+
+    flag = torch.tensor([0.0 if ok else 1.0])
+    dist.all_reduce(flag)
+    return flag.item() == 0.0
+
+
+def run_cell_rank(cell: Cell, device) -> dict:
+    """One rank's part of a cell of ``cell.world`` ranks (the process group is initialised, every
+    rank calls this with the same cell): the read-outs of :func:`run_cell`, returned raw --
+    ``evaluate_cell_world`` holds them to the references in the parent, once for all ranks.
+    Nothing is retried; after an error the ranks agree to end the cell."""
+    import torch.distributed as dist
+
+    rank = dist.get_rank()
+    out = {"cell": cell.id, "rank": rank, "readouts": [], "fails": []}
+    tr = make_trainer(cell, device, rank=rank)
+    try:
+        out["pick"] = [tr.lanes, tr.kernel_waves, tr.groups]
+        out["comm"], out["fallback"] = tr.comm, tr.comm_fallback_reason
+        ok = tr.comm == "xgmi" and tuple(out["pick"]) == cell.expect
+        if not _all_ranks(ok):
+            return out
+        for t in readout_steps(cell):
+            err = None
+            try:
+                if tr.t < t:
+                    dist.barrier()
+                    tr.train(t - tr.t)
+                sg = step_gradient_world(tr)
+                assert sg.t == t
+                out["readouts"].append(tuple(sg))
+            except Exception as e:  # an exchange timeout (tr.synchronize), a launch error
+                err = f"rank {rank} t={t}: {type(e).__name__}: {e}"
+                out["fails"].append(err)
+            if not _all_ranks(err is None):
+                return out
+            if t == 0 and cell.prec == "bf16":
+                tw = make_trainer(cell, device, prec="fp32", rank=rank)
+                try:
+                    out["twin_grad"] = step_gradient_world(tw).grad
+                finally:
+                    tw.close()
+        try:
+            tr.check_comm()
+        except Exception as e:
+            out["fails"].append(f"rank {rank}: {e}")
+        out["step_ctr"], out["t"] = tr.step_ctr.tolist(), tr.t
+        out["comm_after"], out["fallback_after"] = tr.comm, tr.comm_fallback_reason
+    finally:
+        tr.close()
+    return out
+
+
+def evaluate_cell_world(cell: Cell, res: dict) -> tuple[list[dict], list[str]]:
+    """(records, failures) of a cell of several ranks from ``res[rank]`` = :func:`run_cell_rank`'s
+    result: the dispatcher's pick and the exchange in use on every rank, the step counters, the
+    read-out, logged loss and parameters ``torch.equal`` across the ranks (rank-order sums: the
+    protocol's replica guarantee), then rank 0's read-outs against the references."""
+    W = cell.world
+    recs, fails = [], []
+    if sorted(res) != list(range(W)):
+        return [], [f"{cell.id}: results of ranks {sorted(res)}, expected {W}"]
+    steps = readout_steps(cell)
+    for r in range(W):
+        o = res[r]
+        fails += [f"{cell.id}: {m}" for m in o["fails"]]
+        if o["comm"] != "xgmi" or o["fallback"] is not None:
+            fails.append(f"{cell.id} rank {r}: comm {o['comm']!r} (fallback: {o['fallback']})")
+        if tuple(o["pick"]) != cell.expect:
+            fails.append(f"{cell.id} rank {r}: the dispatcher picked (lanes, waves, groups) = {tuple(o['pick'])}, "
+                         f"expected {cell.expect}")
+        if len(o["readouts"]) != len(steps):
+            fails.append(f"{cell.id} rank {r}: {len(o['readouts'])} of {len(steps)} read-outs")
+    if fails:
+        return recs, fails
+    X, Y = cell_data(cell)
+    for r in range(W):
+        o = res[r]
+        if o["comm_after"] != "xgmi" or o["fallback_after"] is not None:
+            fails.append(f"{cell.id} rank {r}: comm {o['comm_after']!r} after the steps")
+        if o["step_ctr"] != [steps[-1] + 1] * N_MODELS or o["t"] != steps[-1] + 1:
+            fails.append(f"{cell.id} rank {r}: step counters {o['step_ctr']}, t = {o['t']}, expected {steps[-1] + 1}")
+    for k, t in enumerate(steps):
+        sgs = [StepGradient(*res[r]["readouts"][k]) for r in range(W)]
+        for r in range(1, W):
+            for name in ("params_before", "grad", "loss", "params_after"):
+                if not torch.equal(getattr(sgs[r], name), getattr(sgs[0], name)):
+                    fails.append(f"{cell.id} t={t}: {name} of rank {r} differs from rank 0's")
+        assert sgs[0].t == t
+        rc, f = evaluate_step(cell, sgs[0], cell_indices(cell, t), X, Y)
+        for x in rc:
+            x["instance"], x["world"] = list(cell.expect), W
+        if t == 0 and cell.prec == "bf16":
+            for i, x in enumerate(rc):
+                g32 = res[0]["twin_grad"]
+                x["vs_fp32_twin"] = max(metric(cell.spec, sgs[0].grad[i], g32[i]).values())
+                if torch.equal(sgs[0].grad[i], g32[i]):
+                    f.append(f"{cell.id} model {i}: the bf16 read-out equals the fp32 twin's")
+        recs += rc
+        fails += f
+    if cell.prec == "bf16":
+        fails += check_bf16(cell, recs)
     return recs, fails
 
 

@@ -147,6 +147,38 @@ def test_fused_split_with_data_parallel_two_ranks():
     assert torch.equal(res[0][0], res[1][0]), "replicas diverged"
 
 
+def _dp_world_rank(rank, world, steps, batch, members):
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    eng, _ = _engine(2, OptimConfig(lr=1e-2), batch=batch, world=world, rank=rank, members=members)
+    assert eng.members == members
+    eng.train(5)
+    eng.train(steps - 5)  # two launches: the exchange epochs carry over
+    eng.synchronize()  # raises on a link / exchange timeout
+    out = eng.flat_params_cpu(), eng.losses(0, steps), [int(s.item()) for s in eng.step]
+    eng.close()
+    return out
+
+
+@pytest.mark.parametrize("world,members", [(3, 0), (4, 0), (4, 2)], ids=["w3-slots", "w4-slots", "w4-g3-members2"])
+def test_fused_split_data_parallel_above_two_ranks(world, members):
+    """2 stages x W DP ranks at batch 100 on the one GPU.  W = 3: 171 samples per rank (the list
+    padded to 513), batches of 100 and 71; W = 4: 128 per rank, batches of 100 and 28.
+    members=0: split_train.hip reduces each stage's gradient over 3 / 4 slots of
+    xgmi_allreduce_slots; members=2: split_lanes.hip over 4 x 2 = 8 slots of xgmi_allreduce_g3,
+    the short batch of 28 leaving the second member of every rank empty.  9 steps cross four
+    epoch edges."""
+    steps = 9
+    res = run_ranks(_dp_world_rank, world, (steps, 100, members), timeout=300)
+    rp, rl = _reference(OptimConfig(lr=1e-2), steps, batch=100, world=world)
+    for r in range(world):
+        torch.testing.assert_close(res[r][1], rl, rtol=1e-4, atol=1e-5)
+        torch.testing.assert_close(res[r][0], rp, rtol=1e-4, atol=2e-5)
+        assert res[r][2] == [steps] * 2
+        assert torch.equal(res[r][0], res[0][0]), f"replica {r} diverged"
+        assert torch.equal(res[r][1], res[0][1]), f"rank {r} logged other losses"
+
+
 @pytest.mark.parametrize("K", [2, 3])
 def test_fused_split_per_stage_launches(K):
     """The launch path of a node with one GPU per stage: every stage its own persistent
