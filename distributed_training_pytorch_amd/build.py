@@ -39,7 +39,8 @@ COMMON_FLAGS = [
 # vs 5.08 us/step with the default occupancy-driven one, docs/perf_notes.md)
 # -ffp-contract=off where the optimizer math lives: every fused multiply-add there is
 # an explicit fmaf, so kernel instances scheduled differently round identically
-SOURCE_FLAGS = {"mlp_train.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contract=off"],
+STEP_SOURCES = ("mlp_train.hip", "mlp_train_one.hip", "mlp_train_lanes.hip")  # the fused step: host, two kernels
+SOURCE_FLAGS = {**{s: ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contract=off"] for s in STEP_SOURCES},
                 "optim.hip": ["-ffp-contract=off"],
                 "split_train.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contract=off"]}
 
@@ -115,10 +116,10 @@ def _compile(src: Path, verbose: bool, full: str) -> Path:
     return obj
 
 
-def variant(name: str, flags: list[str], sources: tuple[str, ...] = ("mlp_train.hip",),
+def variant(name: str, flags: list[str], sources: tuple[str, ...] = STEP_SOURCES,
             verbose: bool = False) -> Path:
     """A/B build: ``sources`` recompiled with extra ``flags`` (e.g. ``-DDTP_ADAM_FAST=0`` with
-    ``sources=("mlp_train.hip", "optim.hip", ...)``: every source that includes ``optim_core.h``) into ``_lib/var_<name>/libdtp.so``, linked with the default objects of every other
+    ``sources=(*STEP_SOURCES, "optim.hip", ...)``: every source that includes ``optim_core.h``) into ``_lib/var_<name>/libdtp.so``, linked with the default objects of every other
     source.  Load it with ``DTP_LIB=<path>`` (``_native.LIB_PATH``)."""
     build(verbose=verbose)
     vdir = LIBDIR / f"var_{name}"
@@ -182,7 +183,7 @@ if __name__ == "__main__":
     if "--variant" in sys.argv:
         i = sys.argv.index("--variant")
         rest = [x for x in sys.argv[i + 2:] if x != "-v"]
-        srcs = ("mlp_train.hip",)
+        srcs = STEP_SOURCES
         if "--sources" in rest:
             j = rest.index("--sources")
             srcs = tuple(rest[j + 1].split(","))

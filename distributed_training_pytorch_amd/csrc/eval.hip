@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kBlock) void mlp_eval_kernel(DtpEvalArgs a) {
     mlp_forward<S>(sw, h, a.slope);
     float l;
     if (ce) {
-      // max-subtracted log-sum-exp minus the target logit (mlp_train.hip's form; the precise
+      // max-subtracted log-sum-exp minus the target logit (the fused step's form; the precise
       // expf / logf: this value is reported, not only differentiated)
       const int cls = (int)a.Y[row];
       float mx = h[S::NL][0];

@@ -1,5 +1,5 @@
 // On-chip all-reduce among the GR workgroups that share ONE model's batch inside one
-// launch (the split-batch step of mlp_train.hip: a model's per-rank batch spread over GR
+// launch (the split-batch step of mlp_train_lanes.hip: a model's per-rank batch spread over GR
 // CUs, each running the several-lanes step on batch / GR samples; and the members of a
 // layer-split stage, split_lanes.hip).
 //

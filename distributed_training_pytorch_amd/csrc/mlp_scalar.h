@@ -1,5 +1,5 @@
 // Weight layouts and per-layer building blocks of the fused train step
-// (mlp_train.hip, mlp_pipe.h): one lane per sample.
+// (mlp_train_one.hip, mlp_pipe.h): one lane per sample.
 //
 //   * LDS forward block of layer l: W_l^T [in][pad4(out)] then bias [pad4(out)], so
 //     consecutive outputs (j, j+1) of one input i are adjacent and

@@ -329,7 +329,7 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
       if (next_local) sl_send(a.act_out, hidx, htag, hv, true);
   }
   bool plain_next = false, plain_prev = false;
-  // per-lane LDS bases (mlp_train.hip's lanes kernel): the part's slice of the blocks, the
+  // per-lane LDS bases (mlp_train_lanes.hip's kernel): the part's slice of the blocks, the
   // sample's slot in a staged operand (+ the part's first row / column), the MFMA reader's
   const float* const wlp = sm.wb + part * NOP;
   const int wslot = (ws & 3) * C::QS + (ws >> 2);

@@ -6,7 +6,8 @@ LeakyReLU, 3x[Linear(10,10), LeakyReLU], Linear(10,1)) is described by an
 ``parameters()`` order (W0, b0, W1, b1, ...), which is what every kernel reads
 and what the data-parallel all-reduce moves in a single message.
 
-CUDA tensors go through the HIP kernels in ``csrc/mlp_train.hip``;
+CUDA tensors go through the HIP kernels in ``csrc/mlp_train_one.hip`` and
+``csrc/mlp_train_lanes.hip`` (picked by ``csrc/mlp_train.hip``);
 CPU tensors (gloo tests, ``--device cpu``) through the PyTorch reference below.
 """
 from __future__ import annotations

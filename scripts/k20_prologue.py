@@ -1,5 +1,5 @@
 """Where the fixed cost of one 20-step launch of the split-batch step goes (the driver's
-K = 20 line): the PROF instance's launch-level stamps (mlp_train.hip lanes kernel, row 0
+K = 20 line): the PROF instance's launch-level stamps (mlp_train_lanes.hip's kernel, row 0
 slots 20 / 18 / 19 / 22 / 23 / 29 / 24 / 21) and its per-step phase stamps (rows 0..7).
 
 Prints, per launch, cycles (s_memtime, shader clock) of: the prologue (entry -> global

@@ -3,7 +3,7 @@
 
 Usage: python scripts/step_loop_stats.py FILE.s KERNEL_SUBSTRING [--json]
 
-FILE.s is what ``build.asm("mlp_train.hip")`` writes.  The step loop is the largest span
+FILE.s is what ``build.asm("mlp_train_lanes.hip")`` (or ``"mlp_train_one.hip"``) writes.  The step loop is the largest span
 of the kernel closed by a backward branch (a branch whose target label stands above it).
 A segment ends with its ``s_barrier``; what follows the last barrier is the tail.
 Instructions are classified by mnemonic prefix only (first match wins):

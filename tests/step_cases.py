@@ -1,5 +1,6 @@
 """The fused step's gradient, read out exactly through the optimizer state, against fp64
-autograd -- one cell per kernel instance the dispatcher of ``csrc/mlp_train.hip`` can pick.
+autograd -- one cell per kernel instance the dispatcher of ``csrc/mlp_train.hip`` can pick from the
+tables of ``csrc/mlp_train_one.hip`` and ``csrc/mlp_train_lanes.hip``.
 
 Shared by ``tests/test_step_matrix_gpu.py``, ``tests/test_xgmi_matrix_gpu.py`` and
 ``tests/test_step_matrix_cpu.py``; CPU-only code except :func:`run_cell` and :func:`run_cell_rank`,
@@ -154,9 +155,9 @@ def _grp(shape, opt, loss, batch, members, **kw):
 
 
 # The dispatcher is resolve_train() in csrc/mlp_train.hip.  A kernel instance added to
-# train_fn() (one lane: FAST or generic, per DTP_TRAIN_SHAPES / DTP_TRAIN_BF16_SHAPES shape),
-# lanes_inst() (2 / 4 lanes, 4 or 8 waves) or grp_inst() / grp_members() (split-batch, the
-# member count a constant at 4) needs a line in INSTANCES below and a cell here that runs it:
+# DTP_ONE_SHAPES in csrc/mlp_train_one.hip (one lane: FAST or generic, per shape and precision)
+# or to DTP_LANES_FAMILIES in csrc/mlp_train_lanes.hip (2 / 4 lanes, 4 or 8 waves; split-batch,
+# the member count a constant at 4) needs a line in INSTANCES below and a cell here that runs it:
 # tests/test_step_matrix_cpu.py::test_every_instance_has_a_cell compares the two.
 CELLS = [
     # ---- one lane, groups="off".  FAST (Adam + MSE, cached data, batch <= 256)
@@ -183,7 +184,7 @@ CELLS = [
     _one("T", "adam", "mse", 256, "fast", prec="bf16"), _one("T", "adam", "mse", 200, "fast", prec="bf16"),
     _one("T", "adam", "mse", 300, "generic", prec="bf16"), _one("C4", "adam", "ce", 256, "generic", prec="bf16"),
     _one("T", "sgd", "mse", 256, "generic", prec="bf16"), _one("T", "sgd", "mse", 64, "generic", prec="bf16"),
-    # the other instances of DTP_TRAIN_BF16_SHAPES' (2,10,5,4)
+    # the other instances of DTP_ONE_SHAPES' bf16 (2,10,5,4)
     _one("C4", "adam", "mse", 256, "fast", prec="bf16"), _one("C4", "adam", "mse", 200, "generic", prec="bf16", cache=False),
     _one("C4", "sgd", "mse", 200, "generic", prec="bf16"), _one("C4", "sgd", "ce", 256, "generic", prec="bf16"),
     # ---- two lanes (batch 65..128, groups="off")
@@ -250,7 +251,7 @@ XGMI_CELLS = (
        _one("H15", "adam", "mse", 200, "fast"), _one("C4", "adam", "mse", 200, "fast"),      # NPT 4, 2
        _one("T", "sgd", "mse", 200, "generic"), _one("C4", "adam", "ce", 200, "generic"),
        _one("C4", "sgd", "ce", 200, "generic"), _one("T", "adam", "mse", 200, "fast", prec="bf16"),
-       # the remaining one-lane instances of train_fn's two xGMI modes (XGMI_INSTANCES)
+       # the remaining one-lane instances of the two xGMI modes (XGMI_INSTANCES)
        _one("T", "adam", "mse", 200, "generic", cache=False), _one("N3", "adam", "mse", 200, "generic", cache=False),
        _one("H15", "adam", "mse", 200, "generic", cache=False), _one("C4", "adam", "mse", 200, "generic", cache=False),
        _one("H15", "sgd", "mse", 200, "generic"), _one("C4", "sgd", "mse", 200, "generic"),
@@ -295,24 +296,24 @@ assert len(BY_ID) == len(ALL_CELLS) + len(ALL_XGMI), "duplicate cell ids"
 
 
 def _xgmi_instances():
-    """What train_fn / lanes_inst / grp_inst instantiate for DTP_MODE_XGMI_ADAM and
-    DTP_MODE_XGMI_SGD, in the form of :func:`_instances` -- written out from those functions,
+    """What the tables (DTP_ONE_SHAPES, DTP_LANES_FAMILIES) instantiate for DTP_MODE_XGMI_ADAM
+    and DTP_MODE_XGMI_SGD, in the form of :func:`_instances` -- written out from the tables,
     NOT derived from XGMI_CELLS."""
     out = []
-    # train_fn: launch_mode<S, XGMI_ADAM, true> (FAST), launch_mode<S, XGMI_ADAM>, launch_mode<S, XGMI_SGD>
+    # one_row(): XGMI_ADAM FAST, XGMI_ADAM, XGMI_SGD
     for prec, shapes in (("fp32", ("T", "N3", "C4", "H15")), ("bf16", ("T", "C4"))):
         for s in shapes:
             out += [(s, 1, 4, "mse", "adam", prec, "fast"), (s, 1, 4, "mse", "adam", prec, "generic"),
                     (s, 1, 4, "mse", "sgd", prec, "generic")]
             if s == "C4":
                 out += [(s, 1, 4, "ce", "adam", prec, "generic"), (s, 1, 4, "ce", "sgd", prec, "generic")]
-    # lanes_modes: every lanes instance has its xGMI twin
+    # lanes_row(): every lanes instance has its xGMI twin
     for L in (2, 4):
         out += [(s, L, 4, "mse", "adam", "fp32", "lanes") for s in ("T", "N3", "C4", "H15")]
         out += [("T", L, 4, "mse", "sgd", "fp32", "lanes"), ("C4", L, 4, "ce", "adam", "fp32", "lanes"),
                 ("C4", L, 4, "ce", "sgd", "fp32", "lanes"), ("T", L, 4, "mse", "adam", "bf16", "lanes"),
                 ("T", L, 8, "mse", "adam", "fp32", "lanes")]
-    # grp_inst: one instance per family (the member count is read at run time); DTP_GRP_NW=8 is
+    # LanesInst.grp[2]: one instance per family (the member count is read at run time); DTP_GRP_NW=8 is
     # one-rank only
     out += [("T", 4, 4, "mse", "adam", "fp32", "grp"), ("T", 4, 4, "mse", "sgd", "fp32", "grp"),
             ("T", 4, 4, "mse", "adam", "bf16", "grp"), ("C4", 4, 4, "ce", "adam", "fp32", "grp"),
@@ -324,11 +325,11 @@ XGMI_INSTANCES = _xgmi_instances()
 
 
 def _instances():
-    """What train_fn / lanes_inst / grp_inst instantiate for the local optimizer modes, as
-    (shape, lanes, waves, loss, optimizer, precision, kind) -- written out from those
-    functions, NOT derived from CELLS.  (The xGMI modes: XGMI_INSTANCES; MODE_GRAD: other tests.)"""
+    """What the tables (DTP_ONE_SHAPES, DTP_LANES_FAMILIES) instantiate for the local optimizer
+    modes, as (shape, lanes, waves, loss, optimizer, precision, kind) -- written out from the
+    tables, NOT derived from CELLS.  (The xGMI modes: XGMI_INSTANCES; MODE_GRAD: other tests.)"""
     out = []
-    # train_fn<Stage<...>>: every DTP_TRAIN_SHAPES shape in fp32, DTP_TRAIN_BF16_SHAPES in bf16;
+    # DTP_ONE_SHAPES: four shapes in fp32, two of them in bf16 too;
     # FAST = Adam + MSE; the generic kernel takes the loss at run time (CE: the 4-class head)
     for prec, shapes in (("fp32", ("T", "N3", "C4", "H15")), ("bf16", ("T", "C4"))):
         for s in shapes:
@@ -336,15 +337,15 @@ def _instances():
                     (s, 1, 4, "mse", "sgd", prec, "generic")]
             if s == "C4":
                 out += [(s, 1, 4, "ce", "adam", prec, "generic"), (s, 1, 4, "ce", "sgd", prec, "generic")]
-    # lanes_inst: Adam + MSE for every shape; SGD + MSE toy; the CE head with Adam and SGD;
+    # DTP_LANES_FAMILIES: Adam + MSE for every shape; SGD + MSE toy; the CE head with Adam and SGD;
     # bf16 toy Adam + MSE; 8 waves: toy fp32 Adam + MSE
     for L in (2, 4):
         out += [(s, L, 4, "mse", "adam", "fp32", "lanes") for s in ("T", "N3", "C4", "H15")]
         out += [("T", L, 4, "mse", "sgd", "fp32", "lanes"), ("C4", L, 4, "ce", "adam", "fp32", "lanes"),
                 ("C4", L, 4, "ce", "sgd", "fp32", "lanes"), ("T", L, 4, "mse", "adam", "bf16", "lanes"),
                 ("T", L, 8, "mse", "adam", "fp32", "lanes")]
-    # grp_inst: toy fp32 Adam / SGD, toy bf16 Adam, the CE head Adam / SGD (each with the
-    # run-time and, through grp_members, the constant member count); DTP_GRP_NW=8: toy Adam
+    # the split-batch families: toy fp32 Adam / SGD, toy bf16 Adam, the CE head Adam / SGD (each
+    # with the run-time and the constant member count, LanesInst.grp[0..1]); DTP_GRP_NW=8: toy Adam
     out += [("T", 4, 4, "mse", "adam", "fp32", "grp"), ("T", 4, 4, "mse", "sgd", "fp32", "grp"),
             ("T", 4, 4, "mse", "adam", "bf16", "grp"), ("C4", 4, 4, "ce", "adam", "fp32", "grp"),
             ("C4", 4, 4, "ce", "sgd", "fp32", "grp"), ("T", 4, 8, "mse", "adam", "fp32", "grp")]
@@ -352,7 +353,7 @@ def _instances():
 
 
 INSTANCES = _instances()
-# the split-batch families whose 4-member instance is a separate template (grp_members)
+# the split-batch families whose 4-member instance is a separate template (LanesInst.grp[1])
 GRP_CONST_FAMILIES = [("T", "mse", "adam", "fp32"), ("T", "mse", "sgd", "fp32"), ("T", "mse", "adam", "bf16"),
                       ("C4", "ce", "adam", "fp32"), ("C4", "ce", "sgd", "fp32")]
 
@@ -426,7 +427,7 @@ def step_gradient(tr: FusedTrainer) -> StepGradient:
 def step_gradient_world(tr: FusedTrainer) -> StepGradient:
     """:func:`step_gradient` on every rank of a W-rank engine at the same step.  Under the
     xGMI modes the optimizer takes the slot-order fp32 sum of the members' gradients times
-    ``grad_scale = 1 / W`` (``mlp_train.hip``: ``g[k] * a.hp.grad_scale``), so with zeroed
+    ``grad_scale = 1 / W`` (the kernels' ``g[k] * a.hp.grad_scale``), so with zeroed
     moments ``tr.m[i]`` is that product bit for bit -- the same bits on every rank.  Every rank
     calls this at the same ``tr.t``; a process-group barrier lets the ranks enter the launch
     together (the exchange's wait is bounded by ``xgmi_timeout_us``)."""

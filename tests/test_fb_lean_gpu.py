@@ -1,4 +1,4 @@
-"""The several-lanes step's leaner loop edge (csrc/mlp_train.hip): the next-but-one sample's
+"""The several-lanes step's leaner loop edge (csrc/mlp_train_lanes.hip): the next-but-one sample's
 permutation word travels raw across the loop's back edge -- and across launches and epochs --
 and its -1 (a batch position past a ragged last batch) is formed at the gather a step later;
 1 / (batch size [x OUT]) is divided once per launch for the full and for the ragged batch and

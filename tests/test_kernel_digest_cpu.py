@@ -99,3 +99,54 @@ def test_descriptor_kernel_set_and_the_rest_of_the_file(tmp_path):
     fn = LISTING.replace("v_add_f32_e32 v0, v0, v0", "v_mul_f32_e32 v0, v0, v0")
     assert m.diff(LISTING, fn) == ["differs    * (outside the kernels)"]
     assert m.main(["--diff", _write(tmp_path, "a.s", LISTING), _write(tmp_path, "b.s", fn)]) == 1
+
+
+# the two kernels with a loop each: basic-block labels .LBB<function ordinal>_<block>
+# and the comments that name them
+LOOPS = LISTING.replace("\tv_mov_b32_e32 v1, 0\n", ".LBB1_1:\n\tv_mov_b32_e32 v1, 0\n\ts_cbranch_scc1 .LBB1_1\n") \
+               .replace("\tv_mov_b32_e32 v1, 1.0\n",
+                        ".LBB2_1:                                ;   in Loop: Header=BB2_1 Depth=1\n"
+                        "\tv_mov_b32_e32 v1, 1.0\n\ts_cbranch_scc1 .LBB2_1\n")
+
+
+def test_the_function_ordinal_alone_is_no_difference_under_the_mask(tmp_path, capsys):
+    m = _mod()
+    assert LOOPS.count(".LBB1_1") == 2 and LOOPS.count(".LBB2_1") == 2 and LOOPS.count("=BB2_1") == 1
+    other = LOOPS.replace("BB1_", "BB7_").replace(".LBB2_1:        ", ".LBB12_1:       ").replace("BB2_", "BB12_")
+    assert m.digests(other, True)[0] == m.digests(LOOPS, True)[0]
+    assert m.diff_kernels([LOOPS], [other]) == []
+    a, b = _write(tmp_path, "a.s", LOOPS), _write(tmp_path, "b.s", other)
+    assert m.main(["--mask-ordinals", "--diff", a, "--", b]) == 0
+    assert capsys.readouterr().out.strip() == "identical"
+    # the default mode stays byte-exact
+    assert m.diff(LOOPS, other) == ["differs    _Z5firstPf", "differs    _Z6secondPf"]
+    assert m.main(["--diff", a, b]) == 1
+    # the listing form: the kernels' lines agree under the mask only
+    rows = []
+    for argv in (["--mask-ordinals", a], ["--mask-ordinals", b], [a], [b]):
+        capsys.readouterr()
+        assert m.main(argv) == 0
+        rows.append(capsys.readouterr().out.splitlines()[:2])
+    assert rows[0] == rows[1] and rows[2] != rows[3]
+
+
+def test_a_block_number_or_an_instruction_still_differs_under_the_mask():
+    m = _mod()
+    block = LOOPS.replace(".LBB2_1", ".LBB2_2")
+    assert m.diff_kernels([LOOPS], [LOOPS.replace("=BB2_1", "=BB2_2")]) == ["differs    _Z6secondPf"]
+    assert m.diff_kernels([LOOPS], [block]) == ["differs    _Z6secondPf"]
+    insn = LOOPS.replace("v_mov_b32_e32 v1, 1.0", "v_mov_b32_e32 v1, 2.0")
+    assert m.diff_kernels([LOOPS], [insn]) == ["differs    _Z6secondPf"]
+
+
+def test_a_kernel_moved_to_a_second_listing_compares_equal(tmp_path, capsys):
+    m = _mod()
+    i, j = LOOPS.index("_Z6secondPf:"), LOOPS.index(".Lfunc_end2:")
+    b1 = LOOPS[:i] + LOOPS[j:]
+    b2 = "\t.text\n" + LOOPS[i:j].replace("BB2_", "BB0_")  # the first function of its own listing
+    assert list(m.digests(b2)[0]) == ["_Z6secondPf"]
+    assert m.diff_kernels([LOOPS], [b1, b2]) == []
+    assert m.diff_kernels([LOOPS], [b1]) == ["only in A  _Z6secondPf"]
+    files = [_write(tmp_path, n, t) for n, t in (("a1.s", LOOPS), ("b1.s", b1), ("b2.s", b2))]
+    assert m.main(["--mask-ordinals", "--diff", files[0], "--", files[1], files[2]]) == 0
+    assert capsys.readouterr().out.strip() == "identical"

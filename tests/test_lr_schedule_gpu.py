@@ -1,5 +1,5 @@
 """Learning-rate schedules in every device code path that applies the rate: the one-lane /
-lanes / split-batch fused steps (csrc/mlp_train.hip), the flat optimizer and the stage backward
+lanes / split-batch fused steps (csrc/mlp_train_one.hip, csrc/mlp_train_lanes.hip), the flat optimizer and the stage backward
 fused with it (csrc/optim.hip, csrc/mlp_stage.hip), the layer-split stages
 (csrc/split_train.hip, csrc/split_lanes.hip).  The flat optimizer, the stage backward and the
 layer-split stages read ``DtpHyper::lr_tab`` by the step counter they hold on the device; the

@@ -1,4 +1,4 @@
-"""The split-batch step's leaner tail (csrc/grp_core.h, mlp_train.hip): exchange addresses
+"""The split-batch step's leaner tail (csrc/grp_core.h, mlp_train_lanes.hip): exchange addresses
 fixed per launch with the buffer parity as a scalar offset, member sums read from every
 member's row alike, the weight scatter through per-launch LDS offsets, the loss log as a
 running offset.  Against autograd + torch.optim (tests/ref_train.py) with the recipe and

@@ -107,8 +107,9 @@ def test_bf16_rounding_model_keeps_parameter_gradients_in_fp32():
 
 
 def test_every_instance_has_a_cell():
-    """Each (shape, lanes, waves, loss, optimizer, precision, kind) that train_fn, lanes_inst and
-    grp_inst of csrc/mlp_train.hip instantiate for the local optimizer modes is run by a cell;
+    """Each (shape, lanes, waves, loss, optimizer, precision, kind) that the tables of
+    csrc/mlp_train_one.hip and csrc/mlp_train_lanes.hip instantiate for the local optimizer
+    modes is run by a cell;
     the split-batch families by a 4-member cell (the constant-count template) and another."""
     have = {c.instance for c in sc.ALL_CELLS}
     missing = [i for i in sc.INSTANCES if i not in have]
@@ -159,7 +160,7 @@ def test_xgmi_cell_inputs_meet_the_conditions(cell):
 
 
 def test_every_xgmi_instance_has_a_cell():
-    """Each instance of train_fn, lanes_inst and grp_inst for DTP_MODE_XGMI_ADAM / _SGD is run by
+    """Each instance of the one-lane and the lanes table for DTP_MODE_XGMI_ADAM / _SGD is run by
     a cell of several ranks, and no cell names an instance that does not exist."""
     have = {c.instance for c in sc.ALL_XGMI}
     missing = [i for i in sc.XGMI_INSTANCES if i not in have]
