@@ -325,11 +325,14 @@ class FusedLayerSplit:
     def __init__(self, spec: MlpSpec, devices: list[torch.device], X: torch.Tensor, Y: torch.Tensor, geom,
                  optim, init_flat: torch.Tensor, boundaries: list[tuple[int, int]] | None = None, group=None,
                  timeout_us: int = 2_000_000, log_cap: int = 1 << 16, sampler: str = "torch",
-                 launch: str = "per_device", members: int | str = "auto"):
+                 launch: str = "per_device", members: int | str = "auto", links: str = "auto"):
         import ctypes
 
         from ..ops.optim import OptimConfig
 
+        if links not in ("auto", "remote"):
+            raise ValueError(f"links={links!r}: auto or remote")
+        self.links = links
         self.spec = spec
         self.devices = [torch.device(d) for d in devices]
         K = len(self.devices)
@@ -370,10 +373,13 @@ class FusedLayerSplit:
         # link buffers: act into stage s+1 (on its device), grad into stage s (on its device).
         # Neighbours on one GPU talk through plain device memory at device scope (the
         # granules meet in the last-level cache); across GPUs through uncached fine-grained
-        # buffers at system scope (xGMI).  DTP_SPLIT_LOCAL_LINKS=0 forces the latter (A/B).
+        # buffers at system scope (xGMI).  DTP_SPLIT_LOCAL_LINKS=0 forces the latter (A/B);
+        # links="remote" gives every link the buffers and scope of a link between two GPUs and
+        # keeps the members' on-GPU plain-store switch off: what a node with one GPU per stage
+        # runs, on whatever devices the stages are given (tests).
         import os
 
-        local_ok = os.environ.get("DTP_SPLIT_LOCAL_LINKS", "1") != "0"
+        local_ok = links == "auto" and os.environ.get("DTP_SPLIT_LOCAL_LINKS", "1") != "0"
         self._owned: list[tuple[int, int]] = []  # (device index, pointer)
         self._link_tensors: list[torch.Tensor] = []
         self.act_buf, self.grad_buf = [None] * K, [None] * K
@@ -477,7 +483,7 @@ class FusedLayerSplit:
                 # bit 2: both ends of this stage's on-GPU links run in this launch, so their
                 # members may switch to plain stores after the XCC hello (split_lanes.hip);
                 # separate per-stage launches keep write-through links (measured faster there)
-                same = all((s2 in stages) for s2 in (s - 1, s + 1) if 0 <= s2 < K)
+                same = links == "auto" and all((s2 in stages) for s2 in (s - 1, s + 1) if 0 <= s2 < K)
                 a.link_local = (int(s > 0 and self.link_local[s - 1])
                                 | (int(s + 1 < K and self.link_local[s]) << 1) | (int(same) << 2))
                 a.smp = geom.to_native()

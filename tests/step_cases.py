@@ -608,8 +608,9 @@ def fp32_margin_abs(spec, p, x, y, n_sum: int) -> torch.Tensor:
     return LAMBDA * var.sqrt()
 
 
-def evaluate_step(cell: Cell, sg: StepGradient, indices: list[int], X, Y) -> tuple[list[dict], list[str]]:
-    """Records (one per model) and failures of one read-out against the references.
+def evaluate_step(cell: Cell, sg: StepGradient, indices: list[int], X, Y,
+                  n_models: int = N_MODELS) -> tuple[list[dict], list[str]]:
+    """Records (one per model, ``n_models`` of them) and failures of one read-out against the references.
 
     A cell of several ranks (``cell.world > 1``) takes one index list per rank, in rank order
     (:func:`cell_indices`): the reference is the mean over the ranks of fp64 autograd on each
@@ -634,7 +635,7 @@ def evaluate_step(cell: Cell, sg: StepGradient, indices: list[int], X, Y) -> tup
             g, lo = g * inv, lo * inv
         return g, lo
 
-    for i in range(N_MODELS):
+    for i in range(n_models):
         p = sg.params_before[i]
         g64, l64 = mean(torch.float64)
         g32, l32 = mean(torch.float32)
