@@ -61,6 +61,11 @@ struct LaneCfg {
   // bf16 compute (Stage BF): matmul operands and outputs rounded to bf16 (mlp_core.h); the
   // dW tiles stay on the exact fp32 MFMA, whose products of bf16 values are exact
   static DTP_DEV float rnd(float v) { return S::rnd(v); }
+  // the fp32 instances' schedule with fewer waits on the layer chain (bias row prefetched
+  // first and one drain per forward layer, K-split accumulators apart until the park, final
+  // tiles parked under the last tile's MFMAs); every part of it measured slower on the bf16
+  // instances (one MFMA per tile, more VALU per chain step), which keep the earlier schedule
+  static constexpr bool CHAIN = !S::BF;
   static constexpr int RW = pad4(H + 1);      // last layer's whole block: row o = W[o][0..H-1], b[o]
   // forward block of partitioned layer l (< NL-1): rows r < din(l) = inputs, row din(l) = bias;
   // a row = [part][NOP] (W[p*NO + k][r] at (r*L + p)*NOP + k)
@@ -120,7 +125,10 @@ struct LFBlk {  // this lane's slice of partitioned forward layer l: din(l) inpu
   template <int R0, int R1>
   DTP_DEV void load(const float* __restrict__ wl, const float* __restrict__ wlp) {
     static_for<R0, (R1 < NR ? R1 : NR)>([&](auto RC) {
-      constexpr int r = decltype(RC)::value;
+      // load order (CHAIN): the bias row (what a layer's chains start from) first, then the input
+      // rows, so the layer starts behind a counted wait that leaves the later rows in flight
+      constexpr int o = decltype(RC)::value;
+      constexpr int r = C::CHAIN ? (o == 0 ? NR - 1 : o - 1) : o;
       static_for<0, NQ>([&](auto QC) {
         constexpr int q = decltype(QC)::value;
         w[r][q] = row_quad<C::NO, q>(wlp + C::f_off(l) + r * C::L * C::NOP);
@@ -138,7 +146,9 @@ struct LLast {  // the last layer whole: OUT rows of [W[o][0..H-1], b[o]]
     static_for<R0, (R1 < NR ? R1 : NR)>([&](auto RC) {
       constexpr int r = decltype(RC)::value;
       static_for<0, NQ>([&](auto QC) {
-        constexpr int q = decltype(QC)::value;
+        // load order (CHAIN): the quad that holds the bias (the row's last) first
+        constexpr int o = decltype(QC)::value;
+        constexpr int q = C::CHAIN ? (o == 0 ? NQ - 1 : o - 1) : o;
         w[r][q] = row_quad<C::H + 1, q>(wl + C::f_last() + r * C::RW);
       });
     });
@@ -215,6 +225,10 @@ DTP_DEV void lane_fwd_layer(const float* wl, const float* wlp, const LFBlk<C, l>
       z[r] = __builtin_elementwise_fma(quad_pair<r % 2>(B.w[i][r / 2]), hi, z[r]);
     });
     __builtin_amdgcn_sched_barrier(0);
+    // the rest of the block, read a layer ago, in ONE drain behind the first chain step: left
+    // to the wait-count pass every later chain step gets a counted wait of its own (an issue
+    // slot each, for rows that landed long ago)
+    if constexpr (C::CHAIN && i == 0) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
     lchunk<i, I>(wl, wlp, p1, p2);
     __builtin_amdgcn_sched_barrier(0);
   });
@@ -265,6 +279,7 @@ DTP_DEV void lane_forward(const float* wl, const float* wlp, const LFBlk<C, l>& 
         z[o] = fmaf(w, st.hin[i], z[o]);
       });
       __builtin_amdgcn_sched_barrier(0);
+      if constexpr (C::CHAIN && i == 0) __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): as in lane_fwd_layer
       lchunk<i, H>(wl, wlp, bt2, none);
       __builtin_amdgcn_sched_barrier(0);
     });

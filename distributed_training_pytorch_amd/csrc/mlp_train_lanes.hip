@@ -373,6 +373,12 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     f32x4 acc[NT];
 #pragma unroll
     for (int q = 0; q < NT; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // C::CHAIN: the second K-split accumulator of every hidden tile, added to the first at the
+    // park: an add behind a layer's last MFMA would wait for it on the input-gradient chain
+    constexpr bool kChain = C::CHAIN;
+    f32x4 acc1[NT];
+#pragma unroll
+    for (int q = 0; q < NT; ++q) acc1[q] = f32x4{0.f, 0.f, 0.f, 0.f};
     const bool valid = nvalid;
     LaneAct<C> st;
     static_for<0, S::IN>([&](auto IC) { st.hin[decltype(IC)::value] = nx[decltype(IC)::value]; });
@@ -498,7 +504,12 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
         lchunk<o, H>(sm.wb, wlp, nb, none);
         __builtin_amdgcn_sched_barrier(0);
       });
-      acc[SC::tile(l)] = a0 + a1;
+      if constexpr (kChain) {
+        acc[SC::tile(l)] = a0;
+        acc1[SC::tile(l)] = a1;
+      } else {
+        acc[SC::tile(l)] = a0 + a1;
+      }
       static_for<0, NO>([&](auto KC) {
         constexpr int k = decltype(KC)::value;
         const float v = S::rnd((k & 1) ? g[k / 2].y : g[k / 2].x);
@@ -517,6 +528,18 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       }
     };
     hidden_rest(hidden_rest, std::integral_constant<int, NL - 2>{}, bt2);
+    // park tile tt of this wave (a hidden tile: the sum of its two accumulators)
+    auto park = [&](auto TC) {
+      constexpr int tt = decltype(TC)::value;
+      f32x4 v = acc[tt];
+      if constexpr (kChain && tt >= 1 && tt <= NL - 2) v = acc[tt] + acc1[tt];  // tile(l) = l there
+      if constexpr (kRows) {  // payload order: every element to its parameter's float (or the sink)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sm.red[wave][rp[tt][e]] = v[e];
+      } else {
+        *reinterpret_cast<f32x4*>(&sm.red[wave][tt * SC::TSZ + SC::tslot(4 * (lane >> 4), lane & 15)]) = v;
+      }
+    };
     {  // layer 0: its dW tile only (packed with the last layer's when they fit)
       float* tl = &sm.stg[wave][lane_area<S>(0)][0];
       static_for<0, NO>([&](auto KC) {
@@ -528,23 +551,23 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       });
       __builtin_amdgcn_wave_barrier();
       const auto to = lane_tile_ops<C>(tl, rdoff);
+      if constexpr (kChain) {
+        // every other tile is final: parked while this one's operands travel and its MFMAs run
+        // (no write moves into a chain; the wave has nothing else to issue here)
+        __builtin_amdgcn_sched_barrier(0);
+        static_for<0, NT>([&](auto TC) {
+          if constexpr (decltype(TC)::value != SC::tile(0)) park(TC);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+      }
       acc[SC::tile(0)] = lane_tile<C, S>(to, acc[SC::tile(0)]);
     }
     DTP_STAMP(8 + wave);
     DTP_STAMP(3);
     {
-      if constexpr (kRows) {  // payload order: every element to its parameter's float (or the sink)
-#pragma unroll
-        for (int tt = 0; tt < NT; ++tt) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) sm.red[wave][rp[tt][e]] = acc[tt][e];
-        }
-      } else {
-        const int q = lane >> 4, col = lane & 15;
-#pragma unroll
-        for (int tt = 0; tt < NT; ++tt)
-          *reinterpret_cast<f32x4*>(&sm.red[wave][tt * SC::TSZ + SC::tslot(4 * q, col)]) = acc[tt];
-      }
+      static_for<0, NT>([&](auto TC) {
+        if constexpr (!kChain || decltype(TC)::value == SC::tile(0)) park(TC);
+      });
       if constexpr (S::BF && DTP_LANES_BFMMA) {
         // the bf16 MFMA saw the loss row's per-sample values truncated to bf16: the wave's
         // loss goes in from a wave sum of the fp32 values instead (same LDS slot, written after;

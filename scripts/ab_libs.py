@@ -3,7 +3,8 @@
 
 Usage: python scripts/ab_libs.py NAME=PATH [NAME=PATH ...] [--reps 3] [--steps 2000 --warmup 200]
        (PATH "default" = the in-tree library).  Runs are interleaved over the variants so
-       clock drift hits every variant alike; prints the median µs/step per variant.
+       clock drift hits every variant alike; prints the median µs/step per variant.  A run
+       that fails ends the session: nothing more is started on the GPU after it.
 """
 from __future__ import annotations
 
@@ -44,6 +45,8 @@ def main():
     for _ in range(a.reps):
         for n, p in libs.items():
             res[n].append(run(p, a.steps, a.warmup, a.extra.split()))
+            if res[n][-1] is None:  # a failed run may have faulted the GPU: start nothing after it
+                raise SystemExit(f"{n}: run failed, stopping")
     out = {n: {"us_per_step": v, "median": statistics.median([x for x in v if x is not None] or [float("nan")])}
            for n, v in res.items()}
     for n, v in out.items():
