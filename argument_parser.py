@@ -33,7 +33,8 @@ def build_parser(description: str | None = None) -> argparse.ArgumentParser:
     clip = p.add_mutually_exclusive_group()
     clip.add_argument("--clip_grad_norm", type=float, default=0.0,
                       help="> 0: clip each model's gradient to this L2 norm before its optimizer step "
-                           "(torch.nn.utils.clip_grad_norm_ per optimizer; the module engine's flat kernel does it)")
+                           "(torch.nn.utils.clip_grad_norm_ per optimizer; on a GPU the fused engine clips inside its "
+                           "step kernel, the module engine inside its flat optimizer kernel)")
     clip.add_argument("--clip_grad_value", type=float, default=0.0,
                       help="> 0: clamp every gradient element to [-F, F] before the optimizer step")
     p.add_argument("--lr_schedule", choices=["constant", "linear", "cosine", "step"], default="constant",

@@ -71,6 +71,11 @@ struct DtpTrainArgs {
   int* grp_status;
   int groups;
   int pad3_;
+  // gradient clipping inside the step (clip_core.h), per model, the update modes only; all
+  // zeros = off.  At most one of max_norm / clip_value may be set; the meaning of DtpOptArgs's.
+  float max_norm;    // > 0: scale model i's gradient by clamp(max_norm / (norm_i + 1e-6), max=1)
+  float clip_value;  // > 0: clamp every element of the gradient * hp.grad_scale to [-clip_value, clip_value]
+  float* norm_out;   // max_norm > 0: [n_models] L2 norm before clipping, of the last step a launch ran
 };
 
 int dtp_version(void);
@@ -85,6 +90,8 @@ int dtp_mlp_train_profile(const DtpTrainArgs* a, void* stream);
 int dtp_mlp_train_profile_lanes(const DtpTrainArgs* a, int lanes, void* stream);
 // lanes per sample of the step instance these arguments select (mlp_lanes.h), 0: none
 int dtp_mlp_train_lanes(const DtpTrainArgs* a, int in, int h, int nl, int out, int mode);
+// 1 when a train engine (dtp_train_engine_create) runs a clip twin, the step that clips in the kernel
+int dtp_train_engine_clip(void* engine);
 long long dtp_xgmi_fused_buffer_bytes(int P, int n_models, int world);
 
 // ---- stage forward / backward (autograd path, layer-split pipeline) ----

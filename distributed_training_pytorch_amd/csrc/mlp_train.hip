@@ -75,6 +75,27 @@ int xgmi_max_slot16(int P) {
   return m;
 }
 
+// does the launch clip its gradient in the kernel (a clip twin, clip_core.h)?
+bool clip_set(const DtpTrainArgs& a) { return a.max_norm > 0.f || a.clip_value > 0.f; }
+
+// DTP_LANES=<L>[x<NW>] as given (L = 0: unset)
+const LanePick& forced_lanes_env() {
+  static const LanePick forced = [] {
+    LanePick f{0, 4};
+    const char* e = getenv("DTP_LANES");
+    if (e) {
+      f.L = atoi(e);
+      const char* x = strchr(e, 'x');
+      if (x) f.NW = atoi(x + 1);
+    }
+    return f;
+  }();
+  return forced;
+}
+// the 8-wave instances have no clip twin: a clipping launch resolves as if DTP_LANES=..x8
+// had not been given
+bool forced_lanes_ignored(const DtpTrainArgs& a) { return clip_set(a) && forced_lanes_env().NW == 8; }
+
 // 4 lanes per sample for per-rank batches <= 64, 2 for <= 128, else the one-lane kernel
 // (L = 1).  DTP_LANES=<L>[x<NW>] forces a choice (A/B runs; NW = 8 runs two waves per
 // SIMD, 512 / L samples); a forced pick whose batch bound does not hold falls back to 1.
@@ -89,7 +110,8 @@ int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow) {
     if (!e) return -1;
     return strcmp(e, "on") == 0 ? 1 : 0;
   }();
-  static const bool forced_lanes = getenv("DTP_LANES") != nullptr;  // a forced lanes instance runs as asked
+  // a forced lanes instance runs as asked
+  const bool forced_lanes = getenv("DTP_LANES") != nullptr && !forced_lanes_ignored(a);
   // the caller's request (DtpTrainArgs.groups before the engine fills it in): 0 policy,
   // 1 on, -1 off; the environment wins (A/B runs)
   const int want = env >= 0 ? env : (a.groups > 0 ? 1 : (a.groups < 0 ? 0 : -1));
@@ -111,16 +133,7 @@ int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow) {
 }
 
 LanePick pick_lanes(const DtpTrainArgs& a, int in, int out, bool fast) {
-  static const LanePick forced = [] {
-    LanePick f{0, 4};
-    const char* e = getenv("DTP_LANES");
-    if (e) {
-      f.L = atoi(e);
-      const char* x = strchr(e, 'x');
-      if (x) f.NW = atoi(x + 1);
-    }
-    return f;
-  }();
+  const LanePick forced = forced_lanes_ignored(a) ? LanePick{0, 4} : forced_lanes_env();
   LanePick r;
   if (!fast || a.smp.n * (in + out) > dtp::kLaneData) return r;
   // the largest batch a step sees: a rank's share of the epoch can be smaller than the
@@ -140,6 +153,10 @@ TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int ou
   const bool base = fast_base_ok(a, in, out);
   const bool fast = fast_path_ok(a, in, out, mode);
   const bool ce = a.loss == DTP_LOSS_CE;
+  // a clipping launch (max_norm / clip_value set): the unclipped launch's pick, then its clip
+  // twin; where the pick has no twin (the 8-wave instances, FAST one-lane) the next candidate
+  // in the same order, down to the generic one-lane twin, which every supported shape has
+  const bool clip = clip_set(a);
   LanePick lp = pick_lanes(a, in, out, base);
   const LanesInst* li = base ? dtp::lanes_inst(in, h, nl, out, a.bf16, ce, mode) : nullptr;
   if (li) {
@@ -148,7 +165,7 @@ TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int ou
     // two-waves-per-SIMD 4-lanes step (8 waves), half the members of the default -- toy
     // fp32 Adam + MSE at one rank (docs/perf_notes.md "Round 6: two members")
     static const bool nw8 = getenv("DTP_GRP_NW") && atoi(getenv("DTP_GRP_NW")) == 8;
-    if (nw8 && gr > 1 && mode == DTP_MODE_ADAM && li->grp8) {
+    if (nw8 && !clip && gr > 1 && mode == DTP_MODE_ADAM && li->grp8) {
       const int b = min(a.smp.batch, a.smp.num_samples);
       const int gr8 = (b + 127) / 128;
       if (gr8 > 1 && a.smp.n * (in + out) <= dtp::kLaneData) {
@@ -157,13 +174,15 @@ TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int ou
       }
     }
     if (gr > 1) {
-      if (TrainLaunchFn f = li->grp[dtp::mode_xgmi(mode) ? 2 : (gr == 4 ? 1 : 0)]) {
+      if (TrainLaunchFn f = (clip ? li->clip_grp : li->grp)[dtp::mode_xgmi(mode) ? 2 : (gr == 4 ? 1 : 0)]) {
         if (pick) *pick = LanePick{4, 4, gr};
         return f;
       }
     }
     if (lp.L > 1) {
-      if (TrainLaunchFn f = li->lanes[lp.NW == 8][lp.L == 4][dtp::mode_xgmi(mode)]) {
+      TrainLaunchFn f = li->lanes[lp.NW == 8][lp.L == 4][dtp::mode_xgmi(mode)];
+      if (clip) f = lp.NW == 4 ? li->clip_lanes[lp.L == 4][dtp::mode_xgmi(mode)] : nullptr;
+      if (f) {
         if (pick) *pick = lp;
         return f;
       }
@@ -172,6 +191,7 @@ TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int ou
   if (pick) *pick = LanePick{};
   const dtp::OneInst* oi = dtp::one_lane_inst(in, h, nl, out, a.bf16);
   if (!oi || mode < DTP_MODE_GRAD || mode > DTP_MODE_XGMI_SGD) return nullptr;
+  if (clip) return oi->clip[mode];
   return fast && oi->fast[mode] ? oi->fast[mode] : oi->fn[mode];
 }
 
@@ -209,6 +229,12 @@ int validate_train(const DtpTrainArgs* a, int mode) {
   if (mode == DTP_MODE_GRAD && !a->grad_out) return set_err(-1, "MODE_GRAD needs grad_out");
   if (mode != DTP_MODE_GRAD && !a->opt_m) return set_err(-1, "optimizer modes need opt_m");
   if ((mode == DTP_MODE_ADAM || mode == DTP_MODE_XGMI_ADAM) && !a->opt_v) return set_err(-1, "Adam needs opt_v");
+  if (a->max_norm < 0.f || a->clip_value < 0.f || a->max_norm != a->max_norm || a->clip_value != a->clip_value)
+    return set_err(-4, "clipping: max_norm and clip_value must not be negative");
+  if (a->max_norm > 0.f && a->clip_value > 0.f) return set_err(-4, "clipping: max_norm and clip_value are exclusive");
+  if (a->max_norm > 0.f && !a->norm_out) return set_err(-5, "clipping by norm needs norm_out");
+  if (mode == DTP_MODE_GRAD && clip_set(*a))
+    return set_err(-4, "MODE_GRAD writes the raw gradient: clipping is for the update modes");
   if (dtp::mode_xgmi(mode)) {
     if (!a->peers || !a->epoch) return set_err(-1, "xGMI modes need the peer table and epoch counters");
     if (a->smp.world < 1 || a->smp.world > dtp::kXgmiMaxWorld || a->smp.rank < 0 || a->smp.rank >= a->smp.world)
@@ -338,6 +364,7 @@ int dtp_train_engine_profile(void* h, int n_steps, int t0, void* prof, void* str
   if (!e || !prof || n_steps <= 0) return set_err(-1, "bad engine profile args");
   if (e->pick.GR <= 1 || e->a.bf16 || e->mode != DTP_MODE_ADAM)
     return set_err(-2, "the engine profile instance is the fp32 split-batch step");
+  if (clip_set(e->a)) return set_err(-2, "the engine profile instance has no clipping twin");
   DtpTrainArgs a = e->a;
   a.n_steps = n_steps;
   a.host_t0 = t0;
@@ -374,6 +401,12 @@ int dtp_train_engine_poison(void* h, int epoch) {
   if (hipMemcpy(e->a.grp_status, w, sizeof w, hipMemcpyHostToDevice) != hipSuccess)
     return set_err(-3, "status write failed");
   return 0;
+}
+
+// 1 when the engine's step is a clip twin (clip_core.h): it clips the gradient in the kernel
+int dtp_train_engine_clip(void* h) {
+  auto* e = static_cast<TrainEngine*>(h);
+  return e ? (clip_set(e->a) ? 1 : 0) : set_err(-1, "null engine");
 }
 
 // lanes per sample of the engine's kernel instance (1 = one lane per sample)

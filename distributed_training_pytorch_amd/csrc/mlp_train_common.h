@@ -69,6 +69,7 @@ struct OneInst {
   TrainLaunchFn fn[5];   // by DtpMode
   TrainLaunchFn fast[5]; // the FAST instance of the mode (the Adam modes), else null
   TrainLaunchFn prof;    // PROF instance (FAST Adam), or null
+  TrainLaunchFn clip[5]; // the clip twin of the generic instance (clip_core.h), the four update modes
 };
 const OneInst* one_lane_inst(int in, int h, int nl, int out, bool bf16);
 
@@ -82,6 +83,9 @@ struct LanesInst {
   TrainLaunchFn grp8;            // split-batch on 8-wave members (DTP_GRP_NW=8 A/B)
   TrainLaunchFn prof[2][2];      // PROF lanes instances [8 waves][L == 4]
   TrainLaunchFn grp_prof[2];     // PROF split-batch instances [4 members as a constant]
+  // the clip twins (clip_core.h) of the 4-wave instances; none of the 8-wave, grp8 and PROF ones
+  TrainLaunchFn clip_lanes[2][2];  // [L == 4 (else 2)][xGMI]
+  TrainLaunchFn clip_grp[3];       // as grp
 };
 // the family that serves `mode` (an optimizer mode), or null
 const LanesInst* lanes_inst(int in, int h, int nl, int out, bool bf16, bool ce, int mode);

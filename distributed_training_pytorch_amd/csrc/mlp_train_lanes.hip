@@ -13,6 +13,7 @@
 #include "mlp_pipe.h"
 #include "mlp_scalar.h"
 #include "optim_core.h"
+#include "clip_core.h"
 #include "xgmi_core.h"
 #include "grp_core.h"
 
@@ -118,9 +119,13 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   constexpr int NTH = 64 * NW;                 // threads of the workgroup
   constexpr int NPT = (S::P + NTH - 1) / NTH;  // parameters owned per thread (optimizer, exchange)
   constexpr int NL = S::NL, P = S::P, NT = SC::NT, NO = C::NO, TS = C::TS, H = S::H;
-  constexpr bool kXgmi = MODE == DTP_MODE_XGMI_ADAM || MODE == DTP_MODE_XGMI_SGD;
-  constexpr bool kAdam = MODE == DTP_MODE_ADAM || MODE == DTP_MODE_XGMI_ADAM;
-  static_assert(MODE != DTP_MODE_GRAD, "the lanes step serves the optimizer modes");
+  // MODE: an update DtpTrainMode, | kModeClip for its clip twin (clip_core.h)
+  constexpr int kMode = mode_base(MODE);
+  constexpr bool kClip = mode_clip(MODE);
+  constexpr bool kXgmi = kMode == DTP_MODE_XGMI_ADAM || kMode == DTP_MODE_XGMI_SGD;
+  constexpr bool kAdam = kMode == DTP_MODE_ADAM || kMode == DTP_MODE_XGMI_ADAM;
+  static_assert(kMode != DTP_MODE_GRAD, "the lanes step serves the optimizer modes");
+  static_assert(!kClip || (NW == 4 && !PROF), "clip twins: the 4-wave instances");
   // GRP with kXgmi: ONE flat exchange over world x groups members (xgmi_core.h)
   static_assert(!CE || S::OUT >= 2, "cross-entropy needs >= 2 classes");
   constexpr int YD = CE ? 1 : S::OUT;  // target floats per sample (a class id for CE)
@@ -364,6 +369,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   // into the quotient of a select, back inside the loop)
   float inv_full = inv_of(0), inv_last = inv_of(blast);
   asm volatile("" : "+v"(inv_full), "+v"(inv_last));
+  [[maybe_unused]] float gnorm = 0.f;  // clip twin: the last step's norm before clipping
   __syncthreads();
   stamp_launch(29);
 
@@ -649,10 +655,23 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       as.step_size = adam_sc.x;
       as.bc2_sqrt = adam_sc.y;
       const float lr = ltab ? adam_sc.x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
+      if constexpr (kClip) {
+        // g[] is final here -- summed over waves, members and ranks, the same bits on every
+        // member and rank -- so each workgroup clips on its own (clip_core.h).  A slot this
+        // thread does not own holds parameter 0's gradient: the norm masks it by index.
+        float x[NPT];
+        gnorm = clip_gradient<NPT, NW>(a, g, x, P, tid, gnorm);
 #pragma unroll
-      for (int k = 0; k < NPT; ++k) {
-        if constexpr (kAdam) adam_update(pw[k], mr[k], vr[k], g[k] * a.hp.grad_scale, as);
-        else sgd_update(pw[k], mr[k], g[k] * a.hp.grad_scale, lr, mom, wd, t0 + it == 0);
+        for (int k = 0; k < NPT; ++k) {
+          if constexpr (kAdam) adam_update(pw[k], mr[k], vr[k], x[k], as);
+          else sgd_update(pw[k], mr[k], x[k], lr, mom, wd, t0 + it == 0);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+          if constexpr (kAdam) adam_update(pw[k], mr[k], vr[k], g[k] * a.hp.grad_scale, as);
+          else sgd_update(pw[k], mr[k], g[k] * a.hp.grad_scale, lr, mom, wd, t0 + it == 0);
+        }
       }
 #pragma unroll
       for (int k = 0; k < NPT; ++k) {
@@ -716,6 +735,9 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     }
   }
   if (tid == 0) a.step[model] = t0 + a.n_steps;
+  if constexpr (kClip) {
+    if (tid == 0 && a.max_norm > 0.f && a.norm_out) a.norm_out[model] = gnorm;
+  }
   if (kXgmi && tid == 0) a.epoch[model] = xepoch;
   if (GRP && !kXgmi && tid == 0) a.grp_epoch[model] = xepoch;
   if (kXgmi && model == 0 && a.status) xgmi_record_wait(a.status, xwait, (unsigned long long)a.n_steps, tid);
@@ -724,7 +746,8 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
 
 // ------------------------------------------------------------------------------
 // The instance table.  (IN, H, NL, OUT, bf16 compute, CE head, SGD, 8-wave, split-batch,
-// A/B and PROF extras): a family has L = 2 and 4, local and xGMI, of its optimizer.
+// A/B and PROF extras): a family has L = 2 and 4, local and xGMI, of its optimizer, and the
+// clip twin (clip_core.h) of each of its 4-wave instances, the split-batch ones included.
 #define DTP_LANES_FAMILIES(X)                                                                         \
   X(2, 10, 5, 1, false, false, false, true, true, true)    /* the flagship: toy model, Adam + MSE */  \
   X(2, 10, 5, 1, false, false, true, false, true, false)   /* toy, SGD */                             \
@@ -757,6 +780,16 @@ constexpr LanesInst lanes_row() {
     r.grp[0] = &launch_lanes<S, 4, M, 4, CE, false, true>;
     r.grp[1] = &launch_lanes<S, 4, M, 4, CE, false, true, 4>;
     r.grp[2] = &launch_lanes<S, 4, XM, 4, CE, false, true>;
+  }
+  {  // the clip twins (clip_core.h) of the 4-wave instances above
+    constexpr int CM = M | kModeClip, CXM = XM | kModeClip;
+    r.clip_lanes[0][0] = &launch_lanes<S, 2, CM, 4, CE>, r.clip_lanes[0][1] = &launch_lanes<S, 2, CXM, 4, CE>;
+    r.clip_lanes[1][0] = &launch_lanes<S, 4, CM, 4, CE>, r.clip_lanes[1][1] = &launch_lanes<S, 4, CXM, 4, CE>;
+    if constexpr (GRP) {
+      r.clip_grp[0] = &launch_lanes<S, 4, CM, 4, CE, false, true>;
+      r.clip_grp[1] = &launch_lanes<S, 4, CM, 4, CE, false, true, 4>;
+      r.clip_grp[2] = &launch_lanes<S, 4, CXM, 4, CE, false, true>;
+    }
   }
   if constexpr (EXTRA) {
     r.grp8 = &launch_lanes<S, 4, M, 8, CE, false, true>;

@@ -12,6 +12,7 @@
 #include "mlp_pipe.h"
 #include "mlp_scalar.h"
 #include "optim_core.h"
+#include "clip_core.h"
 #include "xgmi_core.h"
 
 namespace dtp {
@@ -65,9 +66,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
   __shared__ __align__(16) TrainSmem<S> sm;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int model = blockIdx.x;
-  constexpr bool kUpdate = MODE != DTP_MODE_GRAD;
-  constexpr bool kAdam = MODE == DTP_MODE_ADAM || MODE == DTP_MODE_XGMI_ADAM;
-  constexpr bool kXgmi = MODE == DTP_MODE_XGMI_ADAM || MODE == DTP_MODE_XGMI_SGD;
+  // MODE: a DtpTrainMode, | kModeClip for the clip twin of an update mode (clip_core.h)
+  constexpr int kMode = mode_base(MODE);
+  constexpr bool kClip = mode_clip(MODE);
+  constexpr bool kUpdate = kMode != DTP_MODE_GRAD;
+  constexpr bool kAdam = kMode == DTP_MODE_ADAM || kMode == DTP_MODE_XGMI_ADAM;
+  constexpr bool kXgmi = kMode == DTP_MODE_XGMI_ADAM || kMode == DTP_MODE_XGMI_SGD;
+  static_assert(!kClip || (kUpdate && !PROF && !FAST), "clip twins: the generic update instances");
   unsigned long long* prof = reinterpret_cast<unsigned long long*>(a.status);
   // PROF: kernel entry and exit stamps of the launch (slots 20 and 21 of iteration 0)
   auto stamp_launch = [&](int slot) {
@@ -244,6 +249,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
   if (kAdam || ltab) fill_adam(0);
   stamp_launch(23);
   float* const stg_pack = &sm.stage[wave][0][0];
+  [[maybe_unused]] float gnorm = 0.f;  // clip twin: the last step's norm before clipping
   __syncthreads();  // scattered weight blocks and the Adam table visible to every wave
   stamp_launch(29);
 
@@ -380,7 +386,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
       nxt = gather(it + 1, bpn, keys, tid, bpn.size);
     }
 
-    if constexpr (MODE == DTP_MODE_GRAD) {
+    if constexpr (kMode == DTP_MODE_GRAD) {
 #pragma unroll
       for (int k = 0; k < NPT; ++k) {
         const int p = NPT * tid + k;
@@ -394,10 +400,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
       const float lr = ltab ? adam_sc.x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
       // branch-free over the thread's NPT slots (slots past P hold zeros and store
       // into sm.sink), so the compiler can interleave the slots' dependency chains
+      if constexpr (kClip) {  // the averaged gradient clipped in front of the update (clip_core.h)
+        float x[NPT];
+        gnorm = clip_gradient<NPT, kWaves>(a, g, x, P, tid, gnorm);
 #pragma unroll
-      for (int k = 0; k < NPT; ++k) {
-        if constexpr (kAdam) adam_update(pw[k], mr[k], vr[k], g[k] * a.hp.grad_scale, as);
-        else sgd_update(pw[k], mr[k], g[k] * a.hp.grad_scale, lr, mom, wd, t == 0);
+        for (int k = 0; k < NPT; ++k) {
+          if constexpr (kAdam) adam_update(pw[k], mr[k], vr[k], x[k], as);
+          else sgd_update(pw[k], mr[k], x[k], lr, mom, wd, t == 0);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+          if constexpr (kAdam) adam_update(pw[k], mr[k], vr[k], g[k] * a.hp.grad_scale, as);
+          else sgd_update(pw[k], mr[k], g[k] * a.hp.grad_scale, lr, mom, wd, t == 0);
+        }
       }
 #pragma unroll
       for (int k = 0; k < NPT; ++k) {
@@ -434,6 +450,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
       }
     }
     if (tid == 0) a.step[model] = t0 + a.n_steps;
+    if constexpr (kClip) {
+      if (tid == 0 && a.max_norm > 0.f && a.norm_out) a.norm_out[model] = gnorm;
+    }
     if (kXgmi && tid == 0) a.epoch[model] = xepoch;
     if (kXgmi && model == 0 && a.status) xgmi_record_wait(a.status, xwait, (unsigned long long)a.n_steps, tid);
     stamp_launch(21);
@@ -443,7 +462,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
 // ------------------------------------------------------------------------------
 // The instance table.  (IN, H, NL, OUT, bf16 compute, PROF): every row has all five modes
 // plus the FAST instance of the two Adam modes (the training configuration of the demos and
-// bench.py).
+// bench.py), and the clip twin of the generic instance in the four update modes (a clipped
+// launch has no FAST instance: it runs the generic twin).
 #define DTP_ONE_SHAPES(X)                                                        \
   X(2, 10, 5, 1, false, true)  /* the toy model; the phase-stamp diagnostic */   \
   X(2, 10, 5, 1, true, false)                                                    \
@@ -466,6 +486,10 @@ constexpr OneInst one_row() {
              &launch_one<S, DTP_MODE_XGMI_ADAM, false, true>, nullptr},
             nullptr};
   if constexpr (PROF) r.prof = &launch_one<S, DTP_MODE_ADAM, true, true>;
+  r.clip[DTP_MODE_ADAM] = &launch_one<S, DTP_MODE_ADAM | kModeClip>;
+  r.clip[DTP_MODE_SGD] = &launch_one<S, DTP_MODE_SGD | kModeClip>;
+  r.clip[DTP_MODE_XGMI_ADAM] = &launch_one<S, DTP_MODE_XGMI_ADAM | kModeClip>;
+  r.clip[DTP_MODE_XGMI_SGD] = &launch_one<S, DTP_MODE_XGMI_SGD | kModeClip>;
   return r;
 }
 

@@ -92,6 +92,10 @@ class FusedTrainer:
         self.step_ctr = torch.zeros(n_models, dtype=torch.int32, device=dev)
         self.loss_log = torch.zeros(self.cfg.log_cap, n_models, dtype=torch.float32, device=dev)
         self.comm_buf = torch.zeros(n_models * P + n_models, dtype=torch.float32, device=dev)
+        # clipping by norm: each model's gradient norm before clipping at the last step taken
+        # (float32 [n_models] on the device, filled on every path; not checkpoint state)
+        self.grad_norm = (torch.zeros(n_models, dtype=torch.float32, device=dev)
+                          if self.optim.max_grad_norm > 0 else None)
         self.t = 0  # host mirror of the step counter
         self._idx_stream = EpochIndexStream(geom)
         self._graphs: dict = {}
@@ -169,6 +173,16 @@ class FusedTrainer:
         (``csrc/grp_core.h``: a rank's batch over several CUs per model, 64 samples each,
         their gradients summed on chip); 1 otherwise, 0 without a fused kernel."""
         return self._pick() >> 16
+
+    @property
+    def clip_in_kernel(self) -> bool:
+        """Does the step clip its gradient inside the fused kernel (a clip twin of the step
+        instance, ``csrc/clip_core.h``)?  True for a clipping ``OptimConfig`` on the native
+        single-kernel paths (``comm`` none / xgmi); the RCCL / host path and the CPU reference
+        clip in ``flat_optimizer_step``."""
+        if not self.optim.clips or not self.native or self.comm in ("rccl", "host"):
+            return False
+        return bool(nat.load().dtp_train_engine_clip(self._engine_handle()))
 
     def _pick(self) -> int:
         if not self.native or self.comm in ("rccl", "host"):
@@ -338,6 +352,12 @@ class FusedTrainer:
         if self.cfg.groups not in ("auto", "on", "off"):
             raise ValueError(f"groups {self.cfg.groups!r}: auto, on or off")
         a.groups = {"auto": 0, "on": 1, "off": -1}[self.cfg.groups]
+        if mode != nat.MODE_GRAD and self.optim.clips:
+            # the update modes clip in the kernel (the clip twin of the step instance);
+            # MODE_GRAD writes the raw gradient, clipped by whoever consumes it
+            a.max_norm = max(self.optim.max_grad_norm, 0.0)
+            a.clip_value = max(self.optim.clip_grad_value, 0.0)
+            a.norm_out = nat.ptr(self.grad_norm)
         return a
 
     def _update_mode(self) -> int:
@@ -511,7 +531,7 @@ class FusedTrainer:
         comm_util.all_reduce_(self.comm_buf, self.group)
         flat_optimizer_step(self.params, self.m, self.v, self.step_ctr, self.comm_buf, self.optim,
                             grad_scale=1.0 / self.world, loss_log=self.loss_log, loss_scale=1.0 / self.world,
-                            slope=self.spec.slope)
+                            slope=self.spec.slope, norm_out=self.grad_norm)
 
     def _capture_rccl(self, k: int = 1):
         lib = nat.load()
@@ -557,7 +577,8 @@ class FusedTrainer:
         if self.world > 1:
             comm_util.all_reduce_(buf, self.group)
         flat_optimizer_step(self.params, self.m, self.v, self.step_ctr, buf, self.optim,
-                            grad_scale=1.0 / self.world, loss_log=self.loss_log, loss_scale=1.0 / self.world)
+                            grad_scale=1.0 / self.world, loss_log=self.loss_log, loss_scale=1.0 / self.world,
+                            norm_out=self.grad_norm)
         self.t += 1
 
     # ------------------------------------------------------------------ state / logging
@@ -573,7 +594,9 @@ class FusedTrainer:
     def local_gradients(self) -> tuple[torch.Tensor, torch.Tensor]:
         """This rank's gradient [n_models, P] and mean loss [n_models] of the NEXT step
         (step ``t``'s batch, current weights), from the fused kernel's gradient-only launch
-        (MODE_GRAD): no parameter, moment or step counter changes."""
+        (MODE_GRAD): no parameter, moment or step counter changes.  It is the raw gradient:
+        a clipping ``OptimConfig`` does not touch it (clipping belongs to the update), and
+        ``grad_norm`` keeps the last step's value."""
         if not self.native:
             raise RuntimeError("local_gradients needs the native engine")
         self._ensure_epochs(1)

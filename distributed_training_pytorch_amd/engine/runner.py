@@ -236,8 +236,9 @@ def train(config, env, device, rank, world, group: str = "base-demo") -> dict:
         rank_print(rank, f"fused step kernel has no instance for hidden={config.hidden} depth={config.depth} "
                          f"precision={config.precision}: using the module engine (MFMA GEMM layers)")
         engine = "module"
-    if engine == "fused" and (_clip_norm(config) > 0 or _clip_value(config) > 0):
-        # the fused persistent step has no clipping: the module engine's flat optimizer kernel does it
+    if engine == "fused" and device.type != "cuda" and (_clip_norm(config) > 0 or _clip_value(config) > 0):
+        # on a GPU the fused step clips in its kernel (the clip twins, csrc/clip_core.h); a CPU
+        # run keeps taking the module engine, whose flat optimizer clips
         rank_print(rank, "gradient clipping (--clip_grad_norm / --clip_grad_value) is not in the fused step "
                          "kernel: using the module engine")
         engine = "module"
@@ -352,9 +353,11 @@ def _train_fused(config, device, rank, world, logger, faults) -> dict:
         checkpoint.save({**tr.state_dict(), "engine": "fused", "config": vars(config)}, config.checkpoint_dir, it)
     final = tr.losses(it - 1, it)[0].tolist() if it > 0 else [float("nan")] * 2
     samples = geom.batch * (it - start) * world
+    # clipping by norm: each model's gradient norm at the last step, before clipping
+    gnorm = {"grad_norm": tr.grad_norm.tolist()} if tr.grad_norm is not None else {}
     tr.close()
     return {"final_loss": final, "iters": it, "samples_per_s": samples / max(dt, 1e-9), "engine": "fused",
-            **val.summary(),
+            **gnorm, **val.summary(),
             **({"phases": timer.summary()} if trace_enabled() else {})}
 
 

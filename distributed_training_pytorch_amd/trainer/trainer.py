@@ -653,7 +653,8 @@ class Trainer:
             return None
 
         if self.gradient_clip_val > 0:
-            # the fused engine has no clipping: the module path's flat optimizer kernel does it
+            # the Trainer does not drive the fused engine's clip twins (FusedTrainer with a clipping
+            # OptimConfig): the module path's flat optimizer kernel clips
             why = f"gradient clipping (gradient_clip_val={self.gradient_clip_val:g}) is not in the fused engine"
             no(why)
             if self.global_rank == 0:
