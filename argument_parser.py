@@ -30,6 +30,12 @@ def build_parser(description: str | None = None) -> argparse.ArgumentParser:
     p.add_argument("--optimizer", choices=["adam", "sgd"], default="adam")
     p.add_argument("--momentum", type=float, default=0.0)
     p.add_argument("--weight_decay", type=float, default=0.0)
+    p.add_argument("--accumulate_grad_batches", type=int, default=1,
+                   help="A > 1: one optimizer step consumes A consecutive batches (the gradient is the mean of their "
+                        "mean-loss gradients; clipping, weight decay, the schedule and Adam's bias correction act "
+                        "once per step).  --iters, --eval_every, --checkpoint_every, --log_every, "
+                        "--steps_per_launch and the lr_* flags count optimizer steps.  The fused engine runs the "
+                        "window inside its step kernel")
     clip = p.add_mutually_exclusive_group()
     clip.add_argument("--clip_grad_norm", type=float, default=0.0,
                       help="> 0: clip each model's gradient to this L2 norm before its optimizer step "

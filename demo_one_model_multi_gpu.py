@@ -111,6 +111,10 @@ def main(argv=None):
         # a model's norm would span the stages on several GPUs: not built here
         raise SystemExit("demo_one_model_multi_gpu.py: --clip_grad_norm / --clip_grad_value are not supported with "
                          "a layer-split model (the gradient norm would span the stages' GPUs); use demo.py")
+    if config.accumulate_grad_batches != 1:
+        # the layer-split stage kernels take one batch per step: no accumulation built here
+        raise SystemExit("demo_one_model_multi_gpu.py: --accumulate_grad_batches is not supported with a layer-split "
+                         "model (its stage kernels take one batch per optimizer step); use demo.py")
     if config.eval_every > 0:
         # the evaluation kernel takes whole models; a split model's forward spans the stages' GPUs
         raise SystemExit("demo_one_model_multi_gpu.py: --eval_every is not supported with a layer-split model "

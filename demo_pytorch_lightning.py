@@ -113,6 +113,9 @@ def get_args(argv=None):
                       help="Trainer(gradient_clip_val=F, gradient_clip_algorithm='norm'): per optimizer, before its step")
     clip.add_argument("--clip_grad_value", type=float, default=0.0,
                       help="Trainer(gradient_clip_val=F, gradient_clip_algorithm='value')")
+    p.add_argument("--accumulate_grad_batches", type=int, default=1,
+                   help="Lightning's Trainer argument; the in-repo Trainer takes one batch per optimizer step: a "
+                        "value above 1 is refused (demo.py accumulates)")
     p.add_argument("--lr", type=float, default=1e-3)
     p.add_argument("--lr_schedule", choices=["constant", "linear", "cosine", "step"], default="constant",
                    help="configure_optimizers returns a step-interval LambdaLR over this schedule (argument_parser.py)")
@@ -127,6 +130,9 @@ def get_args(argv=None):
 @record
 def main(argv=None):
     a = get_args(argv)
+    if a.accumulate_grad_batches != 1:
+        raise SystemExit("demo_pytorch_lightning.py: --accumulate_grad_batches is not supported by the in-repo Trainer "
+                         "(one batch per optimizer step); use demo.py")
     # before the first GPU touch (torch.cuda.is_available below): HSA reads the IPC mode once
     bootstrap.configure_collective_env()
     torch.manual_seed(a.seed)

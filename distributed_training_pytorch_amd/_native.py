@@ -98,7 +98,7 @@ class TrainArgs(ctypes.Structure):
         ("grp_epoch", c_void_p),
         ("grp_status", c_void_p),
         ("groups", c_int),
-        ("pad3_", c_int),
+        ("accum", c_int),         # micro-batches per optimizer step (0 or 1: off), csrc/accum_core.h
         ("max_norm", c_float),    # gradient clipping in the step kernel (update modes), as OptArgs's
         ("clip_value", c_float),
         ("norm_out", c_void_p),   # float32 [n_models]: the last step's norm before clipping
@@ -279,6 +279,7 @@ def _declare(lib):
         "dtp_train_engine_lanes": (c_int, [c_void_p]),
         "dtp_train_engine_groups": (c_int, [c_void_p]),
         "dtp_train_engine_clip": (c_int, [c_void_p]),
+        "dtp_train_engine_accum": (c_int, [c_void_p]),
         "dtp_train_engine_profile": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
         "dtp_train_engine_status": (c_int, [c_void_p, P(c_int)]),
         "dtp_mlp_train_lanes": (c_int, [P(TrainArgs), c_int, c_int, c_int, c_int, c_int]),

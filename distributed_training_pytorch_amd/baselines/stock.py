@@ -23,9 +23,14 @@ def plain_toy_model(slope: float = 0.01) -> nn.Module:
 
 class StockLoop:
     def __init__(self, dataset, device, batch: int = 256, seed: int = 0, ddp: bool = True,
-                 clip_grad_norm: float = 0.0, clip_grad_value: float = 0.0, schedule=None):
+                 clip_grad_norm: float = 0.0, clip_grad_value: float = 0.0, schedule=None, accumulate: int = 1):
         """``schedule``: an ``ops.schedule.LrSchedule``; both Adams then follow its values
-        through ``torch.optim.lr_scheduler.LambdaLR`` (stepped after every optimizer step)."""
+        through ``torch.optim.lr_scheduler.LambdaLR`` (stepped after every optimizer step).
+        ``accumulate``: batches per optimizer step, the torch idiom (``loss / A``, ``no_sync`` on
+        DDP for the first ``A - 1`` backwards, the step on the last)."""
+        self.accumulate = int(accumulate)
+        if self.accumulate < 1:
+            raise ValueError("accumulate must be >= 1")
         torch.manual_seed(seed)
         # gradient clipping per model (= per optimizer), torch's own functions; 0 = off
         self.clip_grad_norm = clip_grad_norm
@@ -71,6 +76,8 @@ class StockLoop:
                 self.epoch += 1
 
     def step(self):
+        if self.accumulate > 1:
+            return self._step_accumulating()
         data, target = self._next()
         self.ox.zero_grad(set_to_none=True)
         self.oy.zero_grad(set_to_none=True)
@@ -99,6 +106,42 @@ class StockLoop:
             dist.all_reduce(ry, group=self.gloo)
         self.last = (float(rx) / (b * self.world), float(ry) / (b * self.world))
         self.samples += b
+
+    def _step_accumulating(self):
+        import contextlib
+
+        A = self.accumulate
+        self.ox.zero_grad(set_to_none=True)
+        self.oy.zero_grad(set_to_none=True)
+        sx = sy = 0.0
+        for j in range(A):
+            data, target = self._next()
+            data = data.to(self.device)
+            target = target.to(self.device)
+            hold = j < A - 1 and self.ddp  # no all-reduce before the window's last backward
+            with (self.mx.no_sync() if hold else contextlib.nullcontext()), \
+                    (self.my.no_sync() if hold else contextlib.nullcontext()):
+                lx = self.loss(self.mx(data), target)
+                (lx / A).backward()
+                ly = self.loss(self.my(data), target)
+                (ly / A).backward()
+            sx += float(lx.detach().cpu())
+            sy += float(ly.detach().cpu())
+            self.samples += target.size(0)
+        for m in (self.mx, self.my):
+            if self.clip_grad_norm > 0:
+                torch.nn.utils.clip_grad_norm_(m.parameters(), self.clip_grad_norm)
+            elif self.clip_grad_value > 0:
+                torch.nn.utils.clip_grad_value_(m.parameters(), self.clip_grad_value)
+        self.ox.step()
+        self.oy.step()
+        for s in self.schedulers:
+            s.step()
+        # the step's loss: the mean of the window's mean losses, averaged over the ranks
+        r = torch.tensor([sx / A, sy / A], dtype=torch.float64)
+        if self.gloo is not None:
+            dist.all_reduce(r, group=self.gloo)
+        self.last = (float(r[0]) / self.world, float(r[1]) / self.world)
 
     def forward_eval(self, x):
         """Both models' outputs on x (the bare modules: no DDP bookkeeping for a forward

@@ -70,7 +70,13 @@ struct DtpTrainArgs {
   unsigned* grp_epoch;
   int* grp_status;
   int groups;
-  int pad3_;
+  // gradient accumulation inside the step (accum_core.h), the update modes of the several-lanes
+  // / split-batch kernel: one optimizer step consumes the `accum` consecutive batches
+  // t accum .. t accum + accum - 1 of the sampler order; 0 or 1 = off.  n_steps, host_t0 and the
+  // device counters stay optimizer steps; the caller folds 1 / accum into hp.grad_scale.
+  // (It takes the place of a padding int: the block's size and every other offset are unchanged,
+  // and with them the kernel arguments of every existing instance.)
+  int accum;
   // gradient clipping inside the step (clip_core.h), per model, the update modes only; all
   // zeros = off.  At most one of max_norm / clip_value may be set; the meaning of DtpOptArgs's.
   float max_norm;    // > 0: scale model i's gradient by clamp(max_norm / (norm_i + 1e-6), max=1)
@@ -92,6 +98,8 @@ int dtp_mlp_train_profile_lanes(const DtpTrainArgs* a, int lanes, void* stream);
 int dtp_mlp_train_lanes(const DtpTrainArgs* a, int in, int h, int nl, int out, int mode);
 // 1 when a train engine (dtp_train_engine_create) runs a clip twin, the step that clips in the kernel
 int dtp_train_engine_clip(void* engine);
+// 1 when a train engine runs an accumulation twin (accum_core.h)
+int dtp_train_engine_accum(void* engine);
 long long dtp_xgmi_fused_buffer_bytes(int P, int n_models, int world);
 
 // ---- stage forward / backward (autograd path, layer-split pipeline) ----

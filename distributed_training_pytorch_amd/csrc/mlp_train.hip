@@ -78,6 +78,16 @@ int xgmi_max_slot16(int P) {
 // does the launch clip its gradient in the kernel (a clip twin, clip_core.h)?
 bool clip_set(const DtpTrainArgs& a) { return a.max_norm > 0.f || a.clip_value > 0.f; }
 
+// does the launch run an accumulation twin (accum_core.h)?  DTP_ACCUM_TWIN=1 (read once, for
+// tests and A/B runs) sends a launch without accumulation to the twin too: one micro-batch per step
+bool accum_set(const DtpTrainArgs& a) {
+  static const bool forced = [] {
+    const char* e = getenv("DTP_ACCUM_TWIN");
+    return e && e[0] == '1';
+  }();
+  return a.accum > 1 || forced;
+}
+
 // DTP_LANES=<L>[x<NW>] as given (L = 0: unset)
 const LanePick& forced_lanes_env() {
   static const LanePick forced = [] {
@@ -92,9 +102,11 @@ const LanePick& forced_lanes_env() {
   }();
   return forced;
 }
-// the 8-wave instances have no clip twin: a clipping launch resolves as if DTP_LANES=..x8
-// had not been given
-bool forced_lanes_ignored(const DtpTrainArgs& a) { return clip_set(a) && forced_lanes_env().NW == 8; }
+// the 8-wave instances have no clip twin and no accumulation twin: a clipping or accumulating
+// launch resolves as if DTP_LANES=..x8 had not been given
+bool forced_lanes_ignored(const DtpTrainArgs& a, int mode = DTP_MODE_ADAM) {
+  return (clip_set(a) || (accum_set(a) && mode != DTP_MODE_GRAD)) && forced_lanes_env().NW == 8;
+}
 
 // 4 lanes per sample for per-rank batches <= 64, 2 for <= 128, else the one-lane kernel
 // (L = 1).  DTP_LANES=<L>[x<NW>] forces a choice (A/B runs; NW = 8 runs two waves per
@@ -104,14 +116,14 @@ bool forced_lanes_ignored(const DtpTrainArgs& a) { return clip_set(a) && forced_
 // on 64 samples, their gradients summed on chip.  DTP_GROUPS=1 turns it off (A/B runs).
 // DTP_GROUPS: unset = the measured policy below, "on" = wherever an instance exists,
 // "off" / "0" / "1" = never (A/B runs)
-int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow) {
+int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow, int mode) {
   static const int env = [] {  // -1 policy, 0 off, 1 on
     const char* e = getenv("DTP_GROUPS");
     if (!e) return -1;
     return strcmp(e, "on") == 0 ? 1 : 0;
   }();
   // a forced lanes instance runs as asked
-  const bool forced_lanes = getenv("DTP_LANES") != nullptr && !forced_lanes_ignored(a);
+  const bool forced_lanes = getenv("DTP_LANES") != nullptr && !forced_lanes_ignored(a, mode);
   // the caller's request (DtpTrainArgs.groups before the engine fills it in): 0 policy,
   // 1 on, -1 off; the environment wins (A/B runs)
   const int want = env >= 0 ? env : (a.groups > 0 ? 1 : (a.groups < 0 ? 0 : -1));
@@ -132,8 +144,8 @@ int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow) {
   return gr >= 4 ? gr : 1;
 }
 
-LanePick pick_lanes(const DtpTrainArgs& a, int in, int out, bool fast) {
-  const LanePick forced = forced_lanes_ignored(a) ? LanePick{0, 4} : forced_lanes_env();
+LanePick pick_lanes(const DtpTrainArgs& a, int in, int out, bool fast, int mode) {
+  const LanePick forced = forced_lanes_ignored(a, mode) ? LanePick{0, 4} : forced_lanes_env();
   LanePick r;
   if (!fast || a.smp.n * (in + out) > dtp::kLaneData) return r;
   // the largest batch a step sees: a rank's share of the epoch can be smaller than the
@@ -149,7 +161,7 @@ LanePick pick_lanes(const DtpTrainArgs& a, int in, int out, bool fast) {
 }
 
 TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int out, int mode,
-                            LanePick* pick = nullptr, bool allow_groups = false) {
+                            LanePick* pick = nullptr, bool allow_groups = false, bool* no_twin = nullptr) {
   const bool base = fast_base_ok(a, in, out);
   const bool fast = fast_path_ok(a, in, out, mode);
   const bool ce = a.loss == DTP_LOSS_CE;
@@ -157,15 +169,19 @@ TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int ou
   // twin; where the pick has no twin (the 8-wave instances, FAST one-lane) the next candidate
   // in the same order, down to the generic one-lane twin, which every supported shape has
   const bool clip = clip_set(a);
-  LanePick lp = pick_lanes(a, in, out, base);
+  // an accumulating launch (accum > 1, or DTP_ACCUM_TWIN): the plain launch's pick, then its
+  // accumulation twin, which clips at run time.  A pick without a twin (the one-lane kernel,
+  // an 8-wave instance) is an error, never a plain step: *no_twin names it.
+  const bool accum = accum_set(a) && mode != DTP_MODE_GRAD;
+  LanePick lp = pick_lanes(a, in, out, base, mode);
   const LanesInst* li = base ? dtp::lanes_inst(in, h, nl, out, a.bf16, ce, mode) : nullptr;
   if (li) {
-    const int gr = pick_groups(a, in, out, allow_groups);
+    const int gr = pick_groups(a, in, out, allow_groups, mode);
     // A/B only (DTP_GRP_NW=8): the split-batch step on members of 128 samples, each the
     // two-waves-per-SIMD 4-lanes step (8 waves), half the members of the default -- toy
     // fp32 Adam + MSE at one rank (docs/perf_notes.md "Round 6: two members")
     static const bool nw8 = getenv("DTP_GRP_NW") && atoi(getenv("DTP_GRP_NW")) == 8;
-    if (nw8 && !clip && gr > 1 && mode == DTP_MODE_ADAM && li->grp8) {
+    if (nw8 && !clip && !accum && gr > 1 && mode == DTP_MODE_ADAM && li->grp8) {
       const int b = min(a.smp.batch, a.smp.num_samples);
       const int gr8 = (b + 127) / 128;
       if (gr8 > 1 && a.smp.n * (in + out) <= dtp::kLaneData) {
@@ -174,7 +190,7 @@ TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int ou
       }
     }
     if (gr > 1) {
-      if (TrainLaunchFn f = (clip ? li->clip_grp : li->grp)[dtp::mode_xgmi(mode) ? 2 : (gr == 4 ? 1 : 0)]) {
+      if (TrainLaunchFn f = (accum ? li->accum_grp : clip ? li->clip_grp : li->grp)[dtp::mode_xgmi(mode) ? 2 : (gr == 4 ? 1 : 0)]) {
         if (pick) *pick = LanePick{4, 4, gr};
         return f;
       }
@@ -182,6 +198,7 @@ TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int ou
     if (lp.L > 1) {
       TrainLaunchFn f = li->lanes[lp.NW == 8][lp.L == 4][dtp::mode_xgmi(mode)];
       if (clip) f = lp.NW == 4 ? li->clip_lanes[lp.L == 4][dtp::mode_xgmi(mode)] : nullptr;
+      if (accum) f = lp.NW == 4 ? li->accum_lanes[lp.L == 4][dtp::mode_xgmi(mode)] : nullptr;
       if (f) {
         if (pick) *pick = lp;
         return f;
@@ -189,6 +206,10 @@ TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int ou
     }
   }
   if (pick) *pick = LanePick{};
+  if (accum) {
+    if (no_twin) *no_twin = true;
+    return nullptr;
+  }
   const dtp::OneInst* oi = dtp::one_lane_inst(in, h, nl, out, a.bf16);
   if (!oi || mode < DTP_MODE_GRAD || mode > DTP_MODE_XGMI_SGD) return nullptr;
   if (clip) return oi->clip[mode];
@@ -208,6 +229,15 @@ int check_xbuf(const DtpTrainArgs& a, int in, int h, int nl, int out, int mode, 
     return set_err(-5, m);
   }
   return 0;
+}
+
+// an accumulating launch whose pick has no accumulation twin
+int no_twin_err(const DtpTrainArgs& a) {
+  char m[224];
+  snprintf(m, sizeof m, "gradient accumulation (accum = %d): this launch picks a step instance without an "
+           "accumulation twin (the one-lane kernel: a per-rank batch above 128 without the split-batch step, "
+           "groups off, or a shape / data path the several-lanes step does not serve)", a.accum);
+  return set_err(-6, m);
 }
 
 int validate_train(const DtpTrainArgs* a, int mode) {
@@ -235,6 +265,16 @@ int validate_train(const DtpTrainArgs* a, int mode) {
   if (a->max_norm > 0.f && !a->norm_out) return set_err(-5, "clipping by norm needs norm_out");
   if (mode == DTP_MODE_GRAD && clip_set(*a))
     return set_err(-4, "MODE_GRAD writes the raw gradient: clipping is for the update modes");
+  if (a->accum < 0) return set_err(-4, "accumulation: accum must not be negative");
+  if (a->accum > 1) {
+    if (mode == DTP_MODE_GRAD)
+      return set_err(-4, "MODE_GRAD writes one batch's gradient: accumulation is for the update modes");
+    // the data position is t0 * accum micro-steps, a 32-bit count in the kernel
+    const long long t0 = a->host_t0 >= 0 ? a->host_t0 : 0;
+    if (t0 * a->accum > 0x7fffffffLL || (t0 + a->n_steps) * (long long)a->accum > 0x7fffffffLL ||
+        (long long)a->n_steps * a->accum > 0x7fffffffLL)
+      return set_err(-4, "accumulation: t0 * accum and n_steps * accum must stay below 2^31");
+  }
   if (dtp::mode_xgmi(mode)) {
     if (!a->peers || !a->epoch) return set_err(-1, "xGMI modes need the peer table and epoch counters");
     if (a->smp.world < 1 || a->smp.world > dtp::kXgmiMaxWorld || a->smp.rank < 0 || a->smp.rank >= a->smp.world)
@@ -326,7 +366,9 @@ int dtp_mlp_train(const DtpTrainArgs* a, int in, int h, int nl, int out, int mod
   if (mode == DTP_MODE_GRAD && a->n_steps != 1) return set_err(-4, "MODE_GRAD requires n_steps == 1");
   if (int rc = check_sched_t0(*a, mode, a->host_t0)) return rc;
   LanePick lp;
-  TrainLaunchFn fn = resolve_train(*a, in, h, nl, out, mode, &lp);
+  bool no_twin = false;
+  TrainLaunchFn fn = resolve_train(*a, in, h, nl, out, mode, &lp, false, &no_twin);
+  if (!fn && no_twin) return no_twin_err(*a);
   if (!fn) return set_err(-2, "mlp shape / mode not instantiated for the fused train kernel");
   if (int rc = check_xbuf(*a, in, h, nl, out, mode, lp)) return rc;
   fn(*a, (hipStream_t)stream);
@@ -336,9 +378,11 @@ int dtp_mlp_train(const DtpTrainArgs* a, int in, int h, int nl, int out, int mod
 void* dtp_train_engine_create(const DtpTrainArgs* a, int in, int h, int nl, int out, int mode) {
   if (validate_train(a, mode)) return nullptr;
   LanePick lp;
-  TrainLaunchFn fn = resolve_train(*a, in, h, nl, out, mode, &lp, true);
+  bool no_twin = false;
+  TrainLaunchFn fn = resolve_train(*a, in, h, nl, out, mode, &lp, true, &no_twin);
   if (!fn) {
-    set_err(-2, "mlp shape / mode not instantiated for the fused train kernel");
+    if (no_twin) no_twin_err(*a);
+    else set_err(-2, "mlp shape / mode not instantiated for the fused train kernel");
     return nullptr;
   }
   if (check_xbuf(*a, in, h, nl, out, mode, lp)) return nullptr;
@@ -365,6 +409,7 @@ int dtp_train_engine_profile(void* h, int n_steps, int t0, void* prof, void* str
   if (e->pick.GR <= 1 || e->a.bf16 || e->mode != DTP_MODE_ADAM)
     return set_err(-2, "the engine profile instance is the fp32 split-batch step");
   if (clip_set(e->a)) return set_err(-2, "the engine profile instance has no clipping twin");
+  if (e->a.accum > 1) return set_err(-4, "the profile instances have no accumulation twin");
   DtpTrainArgs a = e->a;
   a.n_steps = n_steps;
   a.host_t0 = t0;
@@ -409,6 +454,12 @@ int dtp_train_engine_clip(void* h) {
   return e ? (clip_set(e->a) ? 1 : 0) : set_err(-1, "null engine");
 }
 
+// 1 when the engine's step is an accumulation twin (accum_core.h)
+int dtp_train_engine_accum(void* h) {
+  auto* e = static_cast<TrainEngine*>(h);
+  return e ? (accum_set(e->a) && e->mode != DTP_MODE_GRAD ? 1 : 0) : set_err(-1, "null engine");
+}
+
 // lanes per sample of the engine's kernel instance (1 = one lane per sample)
 int dtp_train_engine_lanes(void* h) {
   auto* e = static_cast<TrainEngine*>(h);
@@ -431,6 +482,8 @@ int dtp_train_engine_run(void* h, int n_steps, int t0, void* stream) {
   if (n_steps <= 0) return set_err(-1, "n_steps must be positive");
   if (e->mode == DTP_MODE_GRAD && n_steps != 1) return set_err(-4, "MODE_GRAD requires n_steps == 1");
   if (int rc = check_sched_t0(e->a, e->mode, t0)) return rc;  // (dtp_graph_capture_engine runs with t0 = -1)
+  if (e->a.accum > 1 && ((long long)(t0 > 0 ? t0 : 0) + n_steps) * e->a.accum > 0x7fffffffLL)
+    return set_err(-4, "accumulation: t0 * accum and n_steps * accum must stay below 2^31");
   e->a.n_steps = n_steps;
   e->a.host_t0 = t0;
   e->fn(e->a, (hipStream_t)stream);
@@ -441,6 +494,7 @@ void dtp_train_engine_destroy(void* h) { delete static_cast<TrainEngine*>(h); }
 
 // diagnostic: toy shape, Adam, phase stamps into a->status (as u64[n_models][8][16])
 int dtp_mlp_train_profile(const DtpTrainArgs* a, void* stream) {
+  if (a && a->accum > 1) return set_err(-4, "the profile instances have no accumulation twin");
   if (!fast_path_ok(*a, 2, 1, DTP_MODE_ADAM))
     return set_err(-2, "the profile instance is the FAST one: cached dataset, SAMPLER_TABLE sampler");
   dtp::one_lane_inst(2, 10, 5, 1, false)->prof(*a, (hipStream_t)stream);
@@ -452,6 +506,7 @@ int dtp_mlp_train_profile_lanes(const DtpTrainArgs* a, int lanes, void* stream) 
   const int L = lanes & 0xff, NW = lanes >> 8 ? lanes >> 8 : 4;
   if ((L != 2 && L != 4) || (NW != 4 && NW != 8))
     return set_err(-1, "lanes must be 2 or 4 (| waves << 8, waves 4 or 8)");
+  if (a && a->accum > 1) return set_err(-4, "the profile instances have no accumulation twin");
   if (!fast_path_ok(*a, 2, 1, DTP_MODE_ADAM) || min(a->smp.batch, a->smp.num_samples) > 64 * NW / L ||
       a->smp.n * (2 + 1) > dtp::kLaneData)
     return set_err(-2, "the lanes profile instance needs the FAST configuration and batch <= 64 NW / L");

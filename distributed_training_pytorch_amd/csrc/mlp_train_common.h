@@ -86,6 +86,9 @@ struct LanesInst {
   // the clip twins (clip_core.h) of the 4-wave instances; none of the 8-wave, grp8 and PROF ones
   TrainLaunchFn clip_lanes[2][2];  // [L == 4 (else 2)][xGMI]
   TrainLaunchFn clip_grp[3];       // as grp
+  // the accumulation twins (accum_core.h) of the same instances; they clip at run time
+  TrainLaunchFn accum_lanes[2][2];  // [L == 4 (else 2)][xGMI]
+  TrainLaunchFn accum_grp[3];       // as grp
 };
 // the family that serves `mode` (an optimizer mode), or null
 const LanesInst* lanes_inst(int in, int h, int nl, int out, bool bf16, bool ce, int mode);

@@ -14,6 +14,7 @@
 #include "mlp_scalar.h"
 #include "optim_core.h"
 #include "clip_core.h"
+#include "accum_core.h"
 #include "xgmi_core.h"
 #include "grp_core.h"
 
@@ -122,6 +123,10 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   // MODE: an update DtpTrainMode, | kModeClip for its clip twin (clip_core.h)
   constexpr int kMode = mode_base(MODE);
   constexpr bool kClip = mode_clip(MODE);
+  // | kModeAccum for its accumulation twin (accum_core.h): a.accum micro-batches per optimizer
+  // step, clipping behind a run-time branch
+  constexpr bool kAccum = mode_accum(MODE);
+  static_assert(!kAccum || (NW == 4 && !PROF && !kClip), "accumulation twins: the 4-wave instances; they clip at run time");
   constexpr bool kXgmi = kMode == DTP_MODE_XGMI_ADAM || kMode == DTP_MODE_XGMI_SGD;
   constexpr bool kAdam = kMode == DTP_MODE_ADAM || kMode == DTP_MODE_XGMI_ADAM;
   static_assert(kMode != DTP_MODE_GRAD, "the lanes step serves the optimizer modes");
@@ -218,8 +223,12 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
   const bool htab = (kAdam && a.adam_tab && a.host_t0 >= 0) || ltab;
   float2 tabv[kAdamTab / NTH];
   if (htab) adam_tab_load<kAdamTab / NTH, NTH>(a, t0, 0, tid, tabv);
-  int epoch = t0 / smp.steps_per_epoch;
-  int bi = t0 - epoch * smp.steps_per_epoch;
+  // accumulation twin: nacc micro-batches per optimizer step; the data position counts
+  // micro-steps (t0 * nacc), everything indexed by `it` or t0 stays per optimizer step
+  const int nacc = kAccum ? max(a.accum, 1) : 1;
+  const int tm0 = kAccum ? t0 * nacc : t0;
+  int epoch = tm0 / smp.steps_per_epoch;
+  int bi = tm0 - epoch * smp.steps_per_epoch;
   // the sample after next: its permutation word is loaded a whole step before the gather
   // that consumes it, so the word travels raw with `fok` (is this lane's batch position
   // inside that batch?) and the -1 of a position past a ragged batch is formed at the
@@ -375,7 +384,6 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
 
   for (int it = 0; it < a.n_steps; ++it) {
     DTP_STAMP(0);
-    const float inv = bi == blast ? inv_last : inv_full;
     f32x4 acc[NT];
 #pragma unroll
     for (int q = 0; q < NT; ++q) acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -385,6 +393,34 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     f32x4 acc1[NT];
 #pragma unroll
     for (int q = 0; q < NT; ++q) acc1[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // park tile tt of this wave (a hidden tile: the sum of its two accumulators)
+    auto park = [&](auto TC) {
+      constexpr int tt = decltype(TC)::value;
+      f32x4 v = acc[tt];
+      if constexpr (kChain && tt >= 1 && tt <= NL - 2) v = acc[tt] + acc1[tt];  // tile(l) = l there
+      if constexpr (kRows) {  // payload order: every element to its parameter's float (or the sink)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) sm.red[wave][rp[tt][e]] = v[e];
+      } else {
+        *reinterpret_cast<f32x4*>(&sm.red[wave][tt * SC::TSZ + SC::tslot(4 * (lane >> 4), lane & 15)]) = v;
+      }
+    };
+    // accumulation twin: the sample of the window's next micro-batch and the index of the one
+    // after it (next_sample below without the loss log's slot, which counts optimizer steps)
+    auto next_micro = [&]() {
+      roll(epoch, bi);
+      nvalid = fast_gather(fidx, fok, nx, ny);
+      roll(e2, b2);
+      fidx = fast_index(e2, b2);
+    };
+    float inv, lpart;
+    [[maybe_unused]] float lacc = 0.f;  // twin, bf16 MFMA tiles: this lane's scaled losses of the window
+    [[maybe_unused]] int mic = 0;       // twin: micro-batch of the window
+    // one pass per micro-batch of the window (one, but in an accumulation twin): forward, loss
+    // and backward into acc / acc1, which are zeroed once per optimizer step
+    do {
+    inv = bi == blast ? inv_last : inv_full;
+    const bool lastm = !kAccum || ++mic >= nacc;  // wave-uniform: the step's tail follows this pass
     const bool valid = nvalid;
     LaneAct<C> st;
     static_for<0, S::IN>([&](auto IC) { st.hin[decltype(IC)::value] = nx[decltype(IC)::value]; });
@@ -404,7 +440,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     }
     // ---------------- loss (MSE) -> output gradient (every lane of the sample)
     float dzl[S::OUT];
-    float lpart = 0.f;
+    lpart = 0.f;
     if constexpr (!CE) {
       static_for<0, S::OUT>([&](auto JC) {
         constexpr int j = decltype(JC)::value;
@@ -432,6 +468,10 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       });
     }
     DTP_STAMP(2);
+    // accumulation twin: the loss cell sums lpart * inv over the window -- every micro-batch by
+    // its own size -- so it holds the sum of the window's mean losses
+    const float lstage = kAccum ? lpart * inv : lpart;
+    if constexpr (kAccum && S::BF && DTP_LANES_BFMMA) lacc += p0 ? lstage : 0.f;
 
     // ---------------- backward
     float dzp[C::NOP];  // this lane's slice of the current layer's output gradient
@@ -441,7 +481,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       static_for<0, S::OUT>([&](auto JC) {
         put(tl, 0, wslot + (SC::rowoff(l) + decltype(JC)::value) * TS, p0, dzl[decltype(JC)::value]);
       });
-      put(tl, 0, wslot + SC::lossrow() * TS, p0, lpart);
+      put(tl, 0, wslot + SC::lossrow() * TS, p0, lstage);
       static_for<0, NO>([&](auto KC) {
         constexpr int k = decltype(KC)::value;
         put(tl, C::AREA, wpart + (SC::coloff(l) + k) * TS, slot_ok(k), st.own[l - 1][k]);
@@ -491,6 +531,8 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       f32x2 g[C::NPR];
       static_for<0, C::NPR>([&](auto RC) { g[decltype(RC)::value] = f32x2{0.f, 0.f}; });
       f32x4 a0 = acc[SC::tile(l)], a1 = f32x4{0.f, 0.f, 0.f, 0.f};
+      // accumulation twin: the second accumulator carries the window's earlier micro-batches too
+      if constexpr (kAccum && kChain) a1 = acc1[SC::tile(l)];
       constexpr int J0 = 2;
       LNone none;
       static_for<0, H>([&](auto OC) {
@@ -534,18 +576,6 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       }
     };
     hidden_rest(hidden_rest, std::integral_constant<int, NL - 2>{}, bt2);
-    // park tile tt of this wave (a hidden tile: the sum of its two accumulators)
-    auto park = [&](auto TC) {
-      constexpr int tt = decltype(TC)::value;
-      f32x4 v = acc[tt];
-      if constexpr (kChain && tt >= 1 && tt <= NL - 2) v = acc[tt] + acc1[tt];  // tile(l) = l there
-      if constexpr (kRows) {  // payload order: every element to its parameter's float (or the sink)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) sm.red[wave][rp[tt][e]] = v[e];
-      } else {
-        *reinterpret_cast<f32x4*>(&sm.red[wave][tt * SC::TSZ + SC::tslot(4 * (lane >> 4), lane & 15)]) = v;
-      }
-    };
     {  // layer 0: its dW tile only (packed with the last layer's when they fit)
       float* tl = &sm.stg[wave][lane_area<S>(0)][0];
       static_for<0, NO>([&](auto KC) {
@@ -557,7 +587,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       });
       __builtin_amdgcn_wave_barrier();
       const auto to = lane_tile_ops<C>(tl, rdoff);
-      if constexpr (kChain) {
+      if constexpr (kChain && !kAccum) {
         // every other tile is final: parked while this one's operands travel and its MFMAs run
         // (no write moves into a chain; the wave has nothing else to issue here)
         __builtin_amdgcn_sched_barrier(0);
@@ -566,8 +596,25 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
         });
         __builtin_amdgcn_sched_barrier(0);
       }
+      if constexpr (kChain && kAccum) {  // the same, on the window's last micro-batch only
+        if (lastm) {
+          static_for<0, NT>([&](auto TC) {
+            if constexpr (decltype(TC)::value != SC::tile(0)) park(TC);
+          });
+        }
+      }
       acc[SC::tile(0)] = lane_tile<C, S>(to, acc[SC::tile(0)]);
     }
+    if constexpr (kAccum) {
+      // not the window's last micro-batch: on to the next one.  No barrier, no park, no LDS
+      // write outside this wave's staging areas -- the weights in LDS are the window's
+      if (!lastm) {
+        next_micro();
+        continue;
+      }
+    }
+    break;
+    } while (true);
     DTP_STAMP(8 + wave);
     DTP_STAMP(3);
     {
@@ -578,7 +625,8 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
         // the bf16 MFMA saw the loss row's per-sample values truncated to bf16: the wave's
         // loss goes in from a wave sum of the fp32 values instead (same LDS slot, written after;
         // row layout: the loss cell itself went to the sink)
-        const float lw = wave_sum(p0 ? lpart : 0.f);
+        // (accumulation twin: of the window's scaled values)
+        const float lw = wave_sum(kAccum ? lacc : (p0 ? lpart : 0.f));
         if (lane == 0) sm.red[wave][kLossPos] = lw;
       }
     }
@@ -635,7 +683,9 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
           prof[((size_t)blockIdx.x * 8 + it) * 32 + 14] = gp_.rt_pub;
       }
     }
-    const float mean_loss = lsum * inv;  // GRP + xGMI: this member's share of the rank's mean
+    // GRP + xGMI: this member's share of the rank's mean.  Accumulation twin: the sum of the
+    // window's mean losses, scaled already; its 1 / nacc is in hp.grad_scale, applied at the log
+    const float mean_loss = kAccum ? lsum : lsum * inv;
     DTP_STAMP(5);
     float gloss = mean_loss;
     if constexpr (kXgmi) {
@@ -655,7 +705,22 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       as.step_size = adam_sc.x;
       as.bc2_sqrt = adam_sc.y;
       const float lr = ltab ? adam_sc.x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
-      if constexpr (kClip) {
+      if constexpr (kAccum) {
+        // the twin clips behind a run-time branch (block-uniform: it comes from the argument
+        // block), as the clip twin does below; off: the plain update's arithmetic
+        float x[NPT];
+        if (a.max_norm > 0.f || a.clip_value > 0.f) {
+          gnorm = clip_gradient<NPT, NW>(a, g, x, P, tid, gnorm);
+        } else {
+#pragma unroll
+          for (int k = 0; k < NPT; ++k) x[k] = g[k] * a.hp.grad_scale;
+        }
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+          if constexpr (kAdam) adam_update(pw[k], mr[k], vr[k], x[k], as);
+          else sgd_update(pw[k], mr[k], x[k], lr, mom, wd, t0 + it == 0);
+        }
+      } else if constexpr (kClip) {
         // g[] is final here -- summed over waves, members and ranks, the same bits on every
         // member and rank -- so each workgroup clips on its own (clip_core.h).  A slot this
         // thread does not own holds parameter 0's gradient: the norm masks it by index.
@@ -690,11 +755,11 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     // the thread that holds the summed loss logs it (the loss granule's owner: every other
     // thread of a split-batch member only has its own member's share)
     if constexpr (kDiet) {
-      if (llog) a.loss_log[loff] = mean_loss;
+      if (llog) a.loss_log[loff] = kAccum ? mean_loss * a.hp.grad_scale : mean_loss;
       loff += a.n_models;
       loff = loff >= lend ? loff - lend : loff;
     } else if (tid == ((kXgmi || GRP) ? xgmi_loss_tid<NPT>(P, NTH) : 0) && a.loss_log && lead) {
-      const float lg = kXgmi ? gloss * a.hp.grad_scale : mean_loss;
+      const float lg = kXgmi ? gloss * a.hp.grad_scale : (kAccum ? mean_loss * a.hp.grad_scale : mean_loss);
       a.loss_log[(size_t)lslot_now * a.n_models + model] = lg;
     }
     DTP_STAMP(6);
@@ -735,7 +800,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
     }
   }
   if (tid == 0) a.step[model] = t0 + a.n_steps;
-  if constexpr (kClip) {
+  if constexpr (kClip || kAccum) {
     if (tid == 0 && a.max_norm > 0.f && a.norm_out) a.norm_out[model] = gnorm;
   }
   if (kXgmi && tid == 0) a.epoch[model] = xepoch;
@@ -789,6 +854,16 @@ constexpr LanesInst lanes_row() {
       r.clip_grp[0] = &launch_lanes<S, 4, CM, 4, CE, false, true>;
       r.clip_grp[1] = &launch_lanes<S, 4, CM, 4, CE, false, true, 4>;
       r.clip_grp[2] = &launch_lanes<S, 4, CXM, 4, CE, false, true>;
+    }
+  }
+  {  // the accumulation twins (accum_core.h) of the same instances
+    constexpr int AM = M | kModeAccum, AXM = XM | kModeAccum;
+    r.accum_lanes[0][0] = &launch_lanes<S, 2, AM, 4, CE>, r.accum_lanes[0][1] = &launch_lanes<S, 2, AXM, 4, CE>;
+    r.accum_lanes[1][0] = &launch_lanes<S, 4, AM, 4, CE>, r.accum_lanes[1][1] = &launch_lanes<S, 4, AXM, 4, CE>;
+    if constexpr (GRP) {
+      r.accum_grp[0] = &launch_lanes<S, 4, AM, 4, CE, false, true>;
+      r.accum_grp[1] = &launch_lanes<S, 4, AM, 4, CE, false, true, 4>;
+      r.accum_grp[2] = &launch_lanes<S, 4, AXM, 4, CE, false, true>;
     }
   }
   if constexpr (EXTRA) {

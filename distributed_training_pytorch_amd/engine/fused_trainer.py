@@ -56,6 +56,11 @@ class EngineConfig:
     # split-batch step (csrc/grp_core.h: a rank's batch over batch/64 workgroups per model):
     # auto = the measured policy (on for 4 members per model with several ranks), on, off
     groups: str = "auto"
+    # gradient accumulation: one optimizer step consumes `accumulate` consecutive batches of the
+    # rank's sampler order (the gradient is the mean of their mean-loss gradients; clipping,
+    # weight decay, the schedule and Adam's bias correction act once per window).  On the
+    # native single-kernel paths the window runs inside the step kernel (csrc/accum_core.h).
+    accumulate: int = 1
 
 
 class FusedTrainer:
@@ -69,6 +74,9 @@ class FusedTrainer:
         self.cfg = cfg or EngineConfig()
         if self.cfg.precision not in ("fp32", "bf16"):
             raise ValueError(f"precision {self.cfg.precision!r}: fp32 or bf16")
+        self.A = int(self.cfg.accumulate)
+        if self.A < 1 or self.A != self.cfg.accumulate:
+            raise ValueError(f"accumulate {self.cfg.accumulate!r}: an integer >= 1")
         self.geom = geom
         self.group = group
         self.device = X.device
@@ -184,6 +192,20 @@ class FusedTrainer:
             return False
         return bool(nat.load().dtp_train_engine_clip(self._engine_handle()))
 
+    @property
+    def accum_in_kernel(self) -> bool:
+        """Does the step run its window of micro-batches inside the fused kernel (an
+        accumulation twin of the step instance, ``csrc/accum_core.h``)?  True for
+        ``accumulate > 1`` on the native single-kernel paths (``comm`` none / xgmi); the RCCL /
+        host path and the CPU reference sum ``accumulate`` gradient evaluations instead."""
+        if not self.native or self.comm in ("rccl", "host"):
+            return False
+        return bool(nat.load().dtp_train_engine_accum(self._engine_handle()))
+
+    def micro_batches(self, t: int) -> range:
+        """The micro-batches optimizer step ``t`` consumes: arguments of :meth:`step_indices`."""
+        return range(t * self.A, t * self.A + self.A)
+
     def _pick(self) -> int:
         if not self.native or self.comm in ("rccl", "host"):
             return 0
@@ -272,12 +294,11 @@ class FusedTrainer:
 
         try:
             ok, why = True, ""
-            # reference: local grads via MODE_GRAD, host all-reduce, flat optimizer
+            # reference: local grads via MODE_GRAD (the window's, summed), host all-reduce, flat optimizer
             buf = torch.zeros_like(self.comm_buf)
             try:
-                a = self._train_args(1, nat.MODE_GRAD, None)
-                nat.check(lib.dtp_mlp_train(ctypes.byref(a), *self.spec.key[:4], nat.MODE_GRAD, nat.stream_ptr()),
-                          "selftest grad")
+                self._ensure_epochs(1)
+                self._grad_window(lib, "selftest grad")
                 buf.copy_(self.comm_buf)
             except Exception as e:
                 ok, why = False, f"selftest grad: {e}"
@@ -286,8 +307,8 @@ class FusedTrainer:
             if not ok:
                 return False, why or "a peer failed the self-test"
             flat_optimizer_step(self.params, self.m, self.v, self.step_ctr, buf, self.optim,
-                                grad_scale=1.0 / self.world, loss_log=self.loss_log, loss_scale=1.0 / self.world,
-                                slope=self.spec.slope)
+                                grad_scale=1.0 / (self.world * self.A), loss_log=self.loss_log,
+                                loss_scale=1.0 / (self.world * self.A), slope=self.spec.slope)
             ref_p = self.params.clone()
             ref_l = self.loss_log[0].clone()
             # the same step through the in-kernel exchange, twice (both parities); every
@@ -342,8 +363,12 @@ class FusedTrainer:
             nat.LOSS_CE if self.cfg.loss == "ce" else nat.LOSS_MSE,
             int(self.cfg.cache_data), self.cfg.xgmi_timeout_us, int(self.cfg.precision == "bf16"), -1, smp,
             # xGMI modes sum the W gradients in-kernel -> DDP averaging 1/W there;
-            # MODE_GRAD writes local means (the flat optimizer applies 1/W)
-            self._hyper(1.0 / self.world if mode in (nat.MODE_XGMI_ADAM, nat.MODE_XGMI_SGD) else 1.0))
+            # MODE_GRAD writes local means (the flat optimizer applies 1/W).  The update modes
+            # sum a window of A micro-batches in the kernel: its 1/A rides along
+            self._hyper(1.0 if mode == nat.MODE_GRAD else
+                        1.0 / ((self.world if mode in (nat.MODE_XGMI_ADAM, nat.MODE_XGMI_SGD) else 1) * self.A)))
+        if mode != nat.MODE_GRAD and self.A > 1:
+            a.accum = self.A
         tab = getattr(self, "_adam_tab", None)
         if tab is not None:
             a.adam_tab, a.adam_tab_len = nat.ptr(tab), tab.shape[0]
@@ -375,8 +400,9 @@ class FusedTrainer:
             # Python bookkeeping is ~1.5 us of a 20-step call's ~85, scripts/launch_floor.py)
             run, e, di, _, ring, spe = f
             t = self.t
+            A = self.A  # the kernel reads micro-steps t A .. (t + n_steps) A - 1
             if ring is None or ring.kind == "identity" or (
-                    ring.lo <= t // spe and (t + n_steps) // spe <= ring.hi - (ring.E >> 1)):
+                    ring.lo <= (t * A) // spe and ((t + n_steps) * A) // spe <= ring.hi - (ring.E >> 1)):
                 rc = run(e, n_steps, t, nat.raw_stream(di))
                 if rc:
                     nat.check(rc, "dtp_train_engine_run")
@@ -401,6 +427,9 @@ class FusedTrainer:
         while remaining > 0:
             if self.cfg.launch == "persistent":
                 k = min(remaining, self.cfg.steps_per_launch)
+                if self.A > 1 and self._ring is not None and self._ring.kind != "identity":
+                    # a window reads A batches: keep a launch's epochs within half the ring
+                    k = min(k, max(1, ((self._ring.E >> 1) * self.geom.steps_per_epoch) // self.A))
                 self._ensure_epochs(k)
                 self._run_engine(k)
             elif self.cfg.launch == "graph" and not (self.optim.schedule is not None and self.optim.name == "adam"):
@@ -427,9 +456,10 @@ class FusedTrainer:
 
     def _ensure_epochs(self, k: int) -> None:
         """The permutation ring holds every epoch the next k steps read (usually a no-op:
-        the ring is filled ahead; a refill is one stream-ordered copy)."""
+        the ring is filled ahead; a refill is one stream-ordered copy).  A step reads its
+        window of ``accumulate`` micro-batches: the data position counts those."""
         if self._ring is not None:
-            self._ring.ensure(*self._ring.epochs_of_steps(self.t, self.t + k - 1))
+            self._ring.ensure(*self._ring.epochs_of_steps(self.t * self.A, (self.t + k) * self.A - 1))
 
     def _drop_engine(self) -> None:
         """Destroy the native executor and every graph captured on it."""
@@ -512,7 +542,8 @@ class FusedTrainer:
         rccl_graph, all k captured in ONE hipGraph (one host replay per k steps: a
         replay costs ~10 us of host time, more than the step itself)."""
         lib = nat.load()
-        if self.cfg.rccl_graph and self.comm == "rccl":
+        # (an accumulating step gives every gradient launch its micro-step from the host: eager)
+        if self.cfg.rccl_graph and self.comm == "rccl" and self.A == 1:
             g = self._graphs.get(("rccl", k))
             if g is None:
                 g = self._capture_rccl(k)
@@ -524,14 +555,30 @@ class FusedTrainer:
             self._rccl_body(lib)
             self.t += 1
 
-    def _rccl_body(self, lib, idx=None, batch_override=None):
+    def _grad_window(self, lib, what: str = "dtp_mlp_train(grad)", idx=None, batch_override=None):
+        """This rank's gradients and mean losses of step ``self.t`` into ``comm_buf``: one
+        MODE_GRAD launch, or with ``accumulate > 1`` one per micro-batch of the window (the
+        host gives each its micro-step), summed in micro-batch order."""
         a = self._train_args(1, nat.MODE_GRAD, idx, batch_override)
-        nat.check(lib.dtp_mlp_train(ctypes.byref(a), *self.spec.key[:4], nat.MODE_GRAD, nat.stream_ptr()),
-                  "dtp_mlp_train(grad)")
+        if self.A == 1:
+            nat.check(lib.dtp_mlp_train(ctypes.byref(a), *self.spec.key[:4], nat.MODE_GRAD, nat.stream_ptr()), what)
+            return
+        acc = None
+        for u in self.micro_batches(self.t):
+            a.host_t0 = u
+            nat.check(lib.dtp_mlp_train(ctypes.byref(a), *self.spec.key[:4], nat.MODE_GRAD, nat.stream_ptr()), what)
+            if acc is None:
+                acc = self.comm_buf.clone()
+            else:
+                acc.add_(self.comm_buf)
+        self.comm_buf.copy_(acc)
+
+    def _rccl_body(self, lib, idx=None, batch_override=None):
+        self._grad_window(lib, idx=idx, batch_override=batch_override)
         comm_util.all_reduce_(self.comm_buf, self.group)
         flat_optimizer_step(self.params, self.m, self.v, self.step_ctr, self.comm_buf, self.optim,
-                            grad_scale=1.0 / self.world, loss_log=self.loss_log, loss_scale=1.0 / self.world,
-                            slope=self.spec.slope, norm_out=self.grad_norm)
+                            grad_scale=1.0 / (self.world * self.A), loss_log=self.loss_log,
+                            loss_scale=1.0 / (self.world * self.A), slope=self.spec.slope, norm_out=self.grad_norm)
 
     def _capture_rccl(self, k: int = 1):
         lib = nat.load()
@@ -556,10 +603,9 @@ class FusedTrainer:
             return False
 
     # ------------------------------------------------------------------ CPU reference path
-    def _reference_step(self):
-        g = self.geom
-        idx = torch.tensor(self._idx_stream.indices(self.t) if self.cfg.sampler == "torch" else g.indices(self.t),
-                           dtype=torch.long, device=self.device)
+    def _reference_grads(self, u: int) -> torch.Tensor:
+        """[n_models P gradients | n_models mean losses] of micro-batch ``u`` at the current weights."""
+        idx = torch.tensor(self.step_indices(u), dtype=torch.long, device=self.device)
         x, y = self.X[idx], self.Y[idx]
         grads = []
         losses = []
@@ -573,12 +619,18 @@ class FusedTrainer:
             (gp,) = torch.autograd.grad(loss, p)
             grads.append(gp)
             losses.append(loss.detach().reshape(1))
-        buf = torch.cat([torch.stack(grads).reshape(-1), torch.cat(losses)])
+        return torch.cat([torch.stack(grads).reshape(-1), torch.cat(losses)])
+
+    def _reference_step(self):
+        buf = None
+        for u in self.micro_batches(self.t):  # the window's gradients, summed in micro-batch order
+            gu = self._reference_grads(u)
+            buf = gu if buf is None else buf.add_(gu)
         if self.world > 1:
             comm_util.all_reduce_(buf, self.group)
         flat_optimizer_step(self.params, self.m, self.v, self.step_ctr, buf, self.optim,
-                            grad_scale=1.0 / self.world, loss_log=self.loss_log, loss_scale=1.0 / self.world,
-                            norm_out=self.grad_norm)
+                            grad_scale=1.0 / (self.world * self.A), loss_log=self.loss_log,
+                            loss_scale=1.0 / (self.world * self.A), norm_out=self.grad_norm)
         self.t += 1
 
     # ------------------------------------------------------------------ state / logging
@@ -588,7 +640,8 @@ class FusedTrainer:
         self.check_comm()
 
     def step_indices(self, t: int) -> list[int]:
-        """Dataset indices of this rank's batch at step t (the order the kernels read)."""
+        """Dataset indices of this rank's batch t of the sampler order (the order the kernels
+        read): with ``accumulate > 1`` a micro-batch, see :meth:`micro_batches`."""
         return self._idx_stream.indices(t) if self.cfg.sampler == "torch" else self.geom.indices(t)
 
     def local_gradients(self) -> tuple[torch.Tensor, torch.Tensor]:
@@ -596,16 +649,21 @@ class FusedTrainer:
         (step ``t``'s batch, current weights), from the fused kernel's gradient-only launch
         (MODE_GRAD): no parameter, moment or step counter changes.  It is the raw gradient:
         a clipping ``OptimConfig`` does not touch it (clipping belongs to the update), and
-        ``grad_norm`` keeps the last step's value."""
+        ``grad_norm`` keeps the last step's value.  With ``accumulate > 1``: the mean over the
+        step's window of micro-batches, one launch each."""
         if not self.native:
             raise RuntimeError("local_gradients needs the native engine")
         self._ensure_epochs(1)
         lib = nat.load()
+        P, n = self.spec.P, self.n_models
+        if self.A > 1:
+            self._grad_window(lib)
+            buf = self.comm_buf * (1.0 / self.A)
+            return buf[:n * P].view(n, P), buf[n * P:n * P + n]
         a = self._train_args(1, nat.MODE_GRAD, None)
         a.host_t0 = self.t
         nat.check(lib.dtp_mlp_train(ctypes.byref(a), *self.spec.key[:4], nat.MODE_GRAD, nat.stream_ptr()),
                   "dtp_mlp_train(grad)")
-        P, n = self.spec.P, self.n_models
         buf = self.comm_buf.clone()
         return buf[:n * P].view(n, P), buf[n * P:n * P + n]
 
@@ -713,11 +771,16 @@ class FusedTrainer:
     def state_dict(self) -> dict:
         return {"params": self.params.detach().cpu(), "m": self.m.cpu(), "v": self.v.cpu(),
                 "step": self.step_ctr.cpu(), "t": self.t, "spec": self.spec.__dict__,
-                "optim": self.optim.__dict__}
+                "optim": self.optim.__dict__,
+                # the data position is t * accumulate; a state dict without the key counts as 1
+                **({"accumulate": self.A} if self.A > 1 else {})}
 
     def load_state_dict(self, sd: dict):
         # the persistent launch takes its step number (sampler cursor AND Adam bias
         # corrections) from the host mirror t, so the device counters must equal it
+        if int(sd.get("accumulate", 1)) != self.A:  # the data position is t * accumulate
+            raise ValueError(f"checkpoint taken with accumulate = {int(sd.get('accumulate', 1))}, this engine "
+                             f"runs accumulate = {self.A}")
         steps = torch.as_tensor(sd["step"]).reshape(-1).tolist()
         if any(int(s) != int(sd["t"]) for s in steps):
             raise ValueError(f"inconsistent engine state: step counters {steps} but t = {sd['t']}")

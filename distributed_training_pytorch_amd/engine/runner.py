@@ -139,6 +139,13 @@ def _clip_norm(config) -> float:
     return max(float(getattr(config, "clip_grad_norm", 0.0) or 0.0), 0.0)
 
 
+def _accumulate(config) -> int:
+    a = int(getattr(config, "accumulate_grad_batches", 1) or 1)
+    if a < 1:
+        raise SystemExit("--accumulate_grad_batches must be >= 1")
+    return a
+
+
 def _clip_value(config) -> float:
     return max(float(getattr(config, "clip_grad_value", 0.0) or 0.0), 0.0)
 
@@ -242,8 +249,17 @@ def train(config, env, device, rank, world, group: str = "base-demo") -> dict:
         rank_print(rank, "gradient clipping (--clip_grad_norm / --clip_grad_value) is not in the fused step "
                          "kernel: using the module engine")
         engine = "module"
+    summary = None
     if engine == "fused":
         summary = _train_fused(config, device, rank, world, logger, faults)
+        if summary is None:
+            # the fused step accumulates in its several-lanes / split-batch kernel
+            # (csrc/accum_core.h); this run's pick -- the one-lane kernel -- has no such twin
+            rank_print(rank, f"--accumulate_grad_batches {_accumulate(config)}: the fused step instance of this run "
+                             "has no accumulation twin: using the module engine")
+            engine = "module"
+    if summary is not None:
+        pass
     elif engine == "module":
         summary = _train_module(config, device, rank, world, logger, faults)
     else:
@@ -271,8 +287,12 @@ def _train_fused(config, device, rank, world, logger, faults) -> dict:
     init = [ToyModel(hidden=config.hidden, depth=config.depth, out_features=out_f).flat_params.detach().clone()
             for _ in range(2)]
     ecfg = EngineConfig(comm=config.comm, launch=config.launch, steps_per_launch=config.steps_per_launch,
-                        sampler=config.sampler, loss=config.loss, precision=config.precision)
+                        sampler=config.sampler, loss=config.loss, precision=config.precision,
+                        accumulate=_accumulate(config))
     tr = FusedTrainer(spec, 2, X, Y, geom, _optim(config), ecfg, init_params=init)
+    if tr.A > 1 and tr.native and tr.comm not in ("rccl", "host") and tr.lanes == 0:
+        tr.close()  # no accumulation twin for this pick (the same on every rank): the caller falls back
+        return None
     start = 0
     if config.resume and config.checkpoint_dir:
         st = checkpoint.load(config.checkpoint_dir)
@@ -352,12 +372,12 @@ def _train_fused(config, device, rank, world, logger, faults) -> dict:
     if config.checkpoint_dir:
         checkpoint.save({**tr.state_dict(), "engine": "fused", "config": vars(config)}, config.checkpoint_dir, it)
     final = tr.losses(it - 1, it)[0].tolist() if it > 0 else [float("nan")] * 2
-    samples = geom.batch * (it - start) * world
+    samples = geom.batch * (it - start) * world * tr.A
     # clipping by norm: each model's gradient norm at the last step, before clipping
     gnorm = {"grad_norm": tr.grad_norm.tolist()} if tr.grad_norm is not None else {}
     tr.close()
     return {"final_loss": final, "iters": it, "samples_per_s": samples / max(dt, 1e-9), "engine": "fused",
-            **gnorm, **val.summary(),
+            "accumulate_grad_batches": tr.A, **gnorm, **val.summary(),
             **({"phases": timer.summary()} if trace_enabled() else {})}
 
 
@@ -383,6 +403,10 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
     from .graph_step import CapturedStep
     opt = FlatOptimizer(bank.flat, bank.flat_grad, _optim(config))
     lossf = torch.nn.CrossEntropyLoss() if config.loss == "ce" else MSELoss()  # fused drop-in (ops/loss.py)
+    # gradient accumulation, the plain form: A micro-batches per optimizer step, each loss scaled
+    # by 1/A through the backward seed, the first A - 1 backwards under ddp.no_sync(), one
+    # flat-optimizer step; iteration `it` reads batches it A .. it A + A - 1
+    A = _accumulate(config)
     start = 0
     if config.resume and config.checkpoint_dir:
         st = checkpoint.load(config.checkpoint_dir)
@@ -390,6 +414,9 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
             if st.get("engine") != "module":
                 raise RuntimeError(f"{config.checkpoint_dir} holds a {st.get('engine', 'fused')!r}-engine "
                                    "checkpoint; resume it with the same engine")
+            if int(st.get("accumulate", 1)) != A:  # the data position is iteration * A
+                raise ValueError(f"checkpoint taken with --accumulate_grad_batches {int(st.get('accumulate', 1))}, "
+                                 f"this run has {A}")
             with torch.no_grad():
                 bank.flat.copy_(st["params"].to(bank.flat.dtype))
             opt.load_state_dict(st["optim_state"])
@@ -398,7 +425,7 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
 
     def _save(it_done):
         checkpoint.save({"engine": "module", "params": bank.flat.detach(), "optim_state": opt.state_dict(),
-                         "config": vars(config)}, config.checkpoint_dir, it_done)
+                         "accumulate": A, "config": vars(config)}, config.checkpoint_dir, it_done)
 
     pbar = _progress(rank, config.iters, config)
     if pbar is not None and start:
@@ -447,7 +474,7 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
     # is skipped (reset whenever a capture is abandoned: its zeroing never ran)
     grads_clean = [False]
     xb = {}
-    fuse_opt = world == 1 and os.environ.get("DTP_MODULE_FUSE_OPT", "1") != "0"
+    fuse_opt = world == 1 and A == 1 and os.environ.get("DTP_MODULE_FUSE_OPT", "1") != "0"
     seed = _Seeds(device)
     loss_log = os.environ.get("DTP_MODULE_LOSSLOG", "1") != "0"  # A/B: the separate ring put
     sync_flush = os.environ.get("DTP_MODULE_SYNC_FLUSH", "0") == "1"  # A/B: the blocking flush
@@ -489,6 +516,42 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
         if not logged:
             ring.put_device(lx, ly)
 
+    # accumulation: the indices of the window's micro-batches where the host uploads them
+    idx_window = torch.zeros(A, geom.batch, dtype=torch.int64, device=device) if A > 1 else None
+
+    def window_body(sizes):
+        """One optimizer step over the window's micro-batches (``sizes``: their batch sizes)."""
+        if not grads_clean[0]:
+            bank.zero_grad()
+        tx = ty = None
+        for j, size in enumerate(sizes):
+            with timer.phase("data"):
+                if size not in xb:
+                    xb[size] = (torch.empty(size, X.shape[1], device=device),
+                                torch.empty(size, Y.shape[1], device=device))
+                x, y = xb[size]
+                if samp_cfg is not None:  # the device sampler's cursor advances per gather
+                    gather_rows2_sampler(X, Y, samp_cfg, samp_cursor, x, y)
+                else:
+                    gather_rows2(X, Y, idx_window[j, :size], x, y)
+                if config.loss == "ce":
+                    y = y.view(-1).long()
+            with timer.phase("forward"):
+                ox, oy = ddp(x)
+                if isinstance(lossf, MSELoss):
+                    lx, ly, lsum = lossf.pair(ox, oy, y)
+                else:
+                    lx, ly = lossf(ox, y), lossf(oy, y)
+                    lsum = lx + ly
+            with timer.phase("backward+allreduce"):
+                with (ddp.no_sync() if j < len(sizes) - 1 else contextlib.nullcontext()):
+                    lsum.backward(seed.get(lsum.shape, 1.0 / A))  # d (sum_j loss_j / A) / d loss_j
+            tx = lx.detach() if tx is None else tx + lx.detach()
+            ty = ly.detach() if ty is None else ty + ly.detach()
+        with timer.phase("optimizer"):
+            grads_clean[0] = opt.step(zero_grad=True)
+        ring.put_device(tx * (1.0 / A), ty * (1.0 / A))
+
     def _abort():
         grads_clean[0] = False
         ddp.reset_hooks()
@@ -497,7 +560,13 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
     # captured: one rank, xGMI buckets (device-side exchange epochs) or RCCL buckets;
     # not gloo-staged buckets (host-driven)
     graphable = device.type == "cuda" and config.launch != "eager" and not trace_enabled() and ddp.graph_safe()
-    stepper = CapturedStep(step_body, device, enabled=graphable, on_abort=_abort)
+    if A > 1:
+        # the window is captured whole where one rank runs it (nothing is reduced); with several
+        # ranks its single reduction follows A - 1 held-back backwards: run eagerly
+        graphable = graphable and world == 1
+        rank_print(rank, f"accumulation window of {A} micro-batches: "
+                         f"{'captured in one graph' if graphable else 'run eagerly'}")
+    stepper = CapturedStep(step_body if A == 1 else window_body, device, enabled=graphable, on_abort=_abort)
     # the device epoch ring {cursor, the epoch's indices} of the replayed step's gather: one
     # fill per epoch instead of an index copy per step (DTP_MODULE_RING=0: the copies, A/B)
     # better still, the step's indices computed on the device by the engine's own sampler
@@ -512,9 +581,9 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
             samp_cfg = geom.to_native()
             if perm_ring is not None:
                 perm_ring.native(samp_cfg)
-            samp_cursor = torch.full((1,), start, dtype=torch.int64, device=device)
+            samp_cursor = torch.full((1,), start * A, dtype=torch.int64, device=device)
     if (samp_cfg is None and graphable and indexer.can_fill_epoch() and ring_gather_ok(X, Y, geom.batch)
-            and ring_mode != "0"):
+            and ring_mode != "0" and A == 1):  # (a window can span two epochs: the one-epoch ring serves A = 1)
         epoch_ring = torch.zeros(1 + geom.steps_per_epoch * geom.batch, dtype=torch.int64, device=device)
         epoch_ring[0] = geom.batch_pos(start)[1] // geom.batch  # the cursor: the first step's batch in its epoch
     # steady-state clock (the summary's steady_samples_per_s): from the end of step
@@ -528,8 +597,22 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
             torch.cuda.synchronize(device)
             t_steady = time.perf_counter()
         faults.check(it)
+        if A > 1:
+            micro = range(it * A, it * A + A)
+            sizes = tuple(geom.batch_size_at(u) for u in micro)
+            if samp_cfg is not None:
+                eps = (geom.batch_pos(micro[0])[0], geom.batch_pos(micro[-1])[0])
+                if perm_ring is not None and eps != ring_epoch:  # resident before the replay that reads them
+                    perm_ring.ensure(*eps)
+                    ring_epoch = eps
+            else:
+                for j, u in enumerate(micro):
+                    idx_window[j, :sizes[j]].copy_(indexer(u))
+            stepper.run(sizes)
         size = geom.batch_size_at(it)
-        if samp_cfg is not None:
+        if A > 1:
+            pass
+        elif samp_cfg is not None:
             ep = geom.batch_pos(it)[0]
             if perm_ring is not None and ep != ring_epoch:  # resident before the replay that reads it
                 perm_ring.ensure(ep, ep)
@@ -541,7 +624,8 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
                 ring_epoch = ep
         else:
             idx_static[:size].copy_(indexer(it))
-        stepper.run(size)
+        if A == 1:
+            stepper.run(size)
         ring.mark(it)
         if ring.full():
             with timer.phase("loss_reduce"):
@@ -566,7 +650,7 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
     dt = t_end - t0
     steady = None
     if t_steady is not None and config.iters > steady_from:
-        steady = geom.batch * (config.iters - steady_from) * world / max(t_end - t_steady, 1e-9)
+        steady = geom.batch * A * (config.iters - steady_from) * world / max(t_end - t_steady, 1e-9)
     if pbar is not None:
         pbar.close()
     if config.check_replicas:
@@ -574,8 +658,8 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
     if config.checkpoint_dir:
         _save(config.iters)
     return {"final_loss": last, "iters": config.iters,
-            "samples_per_s": geom.batch * (config.iters - start) * world / max(dt, 1e-9),
-            "steady_samples_per_s": steady, "engine": "module", **val.summary(),
+            "samples_per_s": geom.batch * A * (config.iters - start) * world / max(dt, 1e-9),
+            "steady_samples_per_s": steady, "engine": "module", "accumulate_grad_batches": A, **val.summary(),
             "graph_replays": stepper.replays,
             # clipping by norm: each model's gradient norm at the last step, before clipping
             **({"grad_norm": opt.grad_norm.tolist()} if _clip_norm(config) > 0 else {}),
@@ -589,10 +673,10 @@ class _Seeds:
         self.device = device
         self._t: dict = {}
 
-    def get(self, shape):
-        t = self._t.get(tuple(shape))
+    def get(self, shape, value: float = 1.0):
+        t = self._t.get((tuple(shape), value))
         if t is None:
-            t = self._t[tuple(shape)] = torch.ones(shape, dtype=torch.float32, device=self.device)
+            t = self._t[(tuple(shape), value)] = torch.full(shape, value, dtype=torch.float32, device=self.device)
         return t
 
 
@@ -603,7 +687,7 @@ def _train_stock(config, device, rank, world, logger, faults) -> dict:
     ds = _dataset(config, rank)
     loop = StockLoop(ds, device, batch=config.batch_size, seed=config.seed,
                      clip_grad_norm=_clip_norm(config), clip_grad_value=_clip_value(config),
-                     schedule=lr_schedule(config))
+                     schedule=lr_schedule(config), accumulate=_accumulate(config))
     pbar = _progress(rank, config.iters, config)
     timer = PhaseTimer(device)
     val = _Validation(config, ds, rank, world, device, logger)
@@ -632,7 +716,8 @@ def _train_stock(config, device, rank, world, logger, faults) -> dict:
                         config.iters)
     loop.close()
     return {"final_loss": list(loop.last), "iters": config.iters,
-            "samples_per_s": loop.samples * world / max(dt, 1e-9), "engine": "stock", **val.summary(),
+            "samples_per_s": loop.samples * world / max(dt, 1e-9), "engine": "stock",
+            "accumulate_grad_batches": loop.accumulate, **val.summary(),
             **({"phases": timer.summary()} if trace_enabled() else {})}
 
 

@@ -21,6 +21,8 @@ MI355X-first choices:
 """
 from __future__ import annotations
 
+import contextlib
+
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -91,6 +93,7 @@ class FlatDDP(nn.Module):
         self._ready: set = set()
         self._works = []
         self._callback_queued = False
+        self._no_sync = False
         for p in params:
             p.register_post_accumulate_grad_hook(self._hook)
             add_grad_ready_hook(p, self._hook)  # grads the GEMM backward accumulates in place
@@ -185,7 +188,22 @@ class FlatDDP(nn.Module):
     def forward(self, *args, **kwargs):
         return self.module(*args, **kwargs)
 
+    @contextlib.contextmanager
+    def no_sync(self):
+        """``torch.nn.parallel.DistributedDataParallel.no_sync()``: a backward inside the context
+        adds into the flat ``.grad`` views and reduces no bucket (the hooks return at once: no
+        counter moves, no callback is queued); the first backward outside it reduces the
+        accumulated buffer, so a window of A backwards costs one all-reduce per bucket.
+        While it is active the wrapper is not ``graph_safe()``."""
+        old, self._no_sync = self._no_sync, True
+        try:
+            yield
+        finally:
+            self._no_sync = old
+
     def _hook(self, p):
+        if self._no_sync:
+            return
         if not self._callback_queued:
             torch.autograd.Variable._execution_engine.queue_callback(self._finalize)
             self._callback_queued = True
@@ -263,7 +281,9 @@ class FlatDDP(nn.Module):
         one rank, when every bucket goes through the in-kernel xGMI all-reduce (its
         exchange epochs are device counters, so each replay is a fresh exchange), or
         when the remaining buckets ride RCCL (capturable collectives); not when a
-        bucket is staged through gloo on the host."""
+        bucket is staged through gloo on the host; and not inside ``no_sync()``."""
+        if self._no_sync:
+            return False
         if self.world == 1:
             return True
         if all(b in self._xgmi_buckets for b in range(len(self._buckets))):
