@@ -105,6 +105,11 @@ class TrainArgs(ctypes.Structure):
     ]
 
 
+class StepPick(ctypes.Structure):
+    """DtpStepPick: which step a launch or an engine runs (variant: 0 plain, 1 clip twin, 2 accumulation twin)."""
+    _fields_ = [("lanes", c_int), ("waves", c_int), ("groups", c_int), ("variant", c_int)]
+
+
 class StageArgs(ctypes.Structure):
     _fields_ = [
         ("x", c_void_p),
@@ -276,13 +281,10 @@ def _declare(lib):
         "dtp_train_engine_poison": (c_int, [c_void_p, c_int]),
         "dtp_train_engine_run": (c_int, [c_void_p, c_int, c_int, c_void_p]),
         "dtp_train_engine_destroy": (None, [c_void_p]),
-        "dtp_train_engine_lanes": (c_int, [c_void_p]),
-        "dtp_train_engine_groups": (c_int, [c_void_p]),
-        "dtp_train_engine_clip": (c_int, [c_void_p]),
-        "dtp_train_engine_accum": (c_int, [c_void_p]),
+        "dtp_train_engine_pick": (c_int, [c_void_p, P(StepPick)]),
         "dtp_train_engine_profile": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
         "dtp_train_engine_status": (c_int, [c_void_p, P(c_int)]),
-        "dtp_mlp_train_lanes": (c_int, [P(TrainArgs), c_int, c_int, c_int, c_int, c_int]),
+        "dtp_mlp_train_pick": (c_int, [P(TrainArgs), c_int, c_int, c_int, c_int, c_int, P(StepPick)]),
         "dtp_mlp_train_profile_lanes": (c_int, [P(TrainArgs), c_int, c_void_p]),
         "dtp_mlp_stage_fwd": (c_int, [P(StageArgs), c_int, c_int, c_int, c_int, c_int, c_void_p]),
         "dtp_mlp_stage_fwd_multi": (c_int, [P(StageMulti), c_int, c_int, c_int, c_int, c_int, c_void_p]),

@@ -39,7 +39,9 @@ COMMON_FLAGS = [
 # vs 5.08 us/step with the default occupancy-driven one, docs/perf_notes.md)
 # -ffp-contract=off where the optimizer math lives: every fused multiply-add there is
 # an explicit fmaf, so kernel instances scheduled differently round identically
-STEP_SOURCES = ("mlp_train.hip", "mlp_train_one.hip", "mlp_train_lanes.hip")  # the fused step: host, two kernels
+# the fused step: host, the one-lane kernel, the lanes kernel's plain instances and its two twins
+STEP_SOURCES = ("mlp_train.hip", "mlp_train_one.hip", "mlp_train_lanes.hip", "mlp_train_lanes_clip.hip",
+                "mlp_train_lanes_accum.hip")
 SOURCE_FLAGS = {**{s: ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contract=off"] for s in STEP_SOURCES},
                 "optim.hip": ["-ffp-contract=off"],
                 "split_train.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contract=off"]}

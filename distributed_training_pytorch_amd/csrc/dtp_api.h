@@ -94,12 +94,17 @@ int dtp_mlp_train_bf16_supported(int in, int h, int nl, int out);
 int dtp_mlp_train(const DtpTrainArgs* a, int in, int h, int nl, int out, int mode, void* stream);
 int dtp_mlp_train_profile(const DtpTrainArgs* a, void* stream);
 int dtp_mlp_train_profile_lanes(const DtpTrainArgs* a, int lanes, void* stream);
-// lanes per sample of the step instance these arguments select (mlp_lanes.h), 0: none
-int dtp_mlp_train_lanes(const DtpTrainArgs* a, int in, int h, int nl, int out, int mode);
-// 1 when a train engine (dtp_train_engine_create) runs a clip twin, the step that clips in the kernel
-int dtp_train_engine_clip(void* engine);
-// 1 when a train engine runs an accumulation twin (accum_core.h)
-int dtp_train_engine_accum(void* engine);
+// Which step a launch or an engine runs: lanes per sample (1: the one-lane kernel, 2 / 4: the
+// several-lanes step, mlp_lanes.h), waves per workgroup, workgroups per model (> 1: the
+// split-batch step, grp_core.h) and variant (0 plain, 1 the clip twin, clip_core.h, 2 the
+// accumulation twin, accum_core.h).
+struct DtpStepPick {
+  int lanes, waves, groups, variant;
+};
+// the step a train engine would run for these arguments: 0, or the error code that
+// dtp_train_engine_create would leave, with *out zeroed
+int dtp_mlp_train_pick(const DtpTrainArgs* a, int in, int h, int nl, int out, int mode, DtpStepPick* out_pick);
+int dtp_train_engine_pick(void* engine, DtpStepPick* out_pick);
 long long dtp_xgmi_fused_buffer_bytes(int P, int n_models, int world);
 
 // ---- stage forward / backward (autograd path, layer-split pipeline) ----

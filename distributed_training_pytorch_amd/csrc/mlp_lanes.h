@@ -1,4 +1,4 @@
-// Fused train step with SEVERAL LANES PER SAMPLE (mlp_train_lanes.hip includes this).
+// Fused train step with SEVERAL LANES PER SAMPLE (mlp_train_lanes_kernel.h includes this).
 //
 // Why: the one-lane-per-sample step (mlp_train_kernel) is latency-bound, so its time
 // does not depend on the batch: 4.26 / 4.30 / 4.27 us at B = 64 / 128 / 256

@@ -30,16 +30,44 @@ using dtp::check_launch;
 using dtp::set_err;
 using dtp::LanesInst;
 using dtp::TrainLaunchFn;
+using dtp::StepVariant;
+using dtp::kPlain;
+using dtp::kClip;
+using dtp::kAccum;
+
+// The forcing variables (A/B runs and tests), read once per process.
+struct StepEnv {
+  bool no_fast = false;     // DTP_FAST=0: no launch takes a FAST, several-lanes or split-batch instance
+  bool accum_twin = false;  // DTP_ACCUM_TWIN=1: a launch without accumulation runs the accumulation twin too
+  int L = 0, NW = 4;        // DTP_LANES=<L>[x<NW>] as given (L = 0: not a number); lanes_set: given at all
+  bool lanes_set = false;
+  int groups = -1;          // DTP_GROUPS: unset = the measured policy (-1), "on" = wherever an instance
+                            // exists (1), anything else ("off" / "0" / "1") = never (0)
+  bool grp_nw8 = false;     // DTP_GRP_NW=8: the split-batch A/B instance on 8-wave members
+};
+const StepEnv& step_env() {
+  static const StepEnv env = [] {
+    StepEnv e;
+    const char* v;
+    if ((v = getenv("DTP_FAST"))) e.no_fast = v[0] == '0';
+    if ((v = getenv("DTP_ACCUM_TWIN"))) e.accum_twin = v[0] == '1';
+    if ((v = getenv("DTP_LANES"))) {
+      e.lanes_set = true;
+      e.L = atoi(v);
+      if (const char* x = strchr(v, 'x')) e.NW = atoi(x + 1);
+    }
+    if ((v = getenv("DTP_GROUPS"))) e.groups = strcmp(v, "on") == 0 ? 1 : 0;
+    if ((v = getenv("DTP_GRP_NW"))) e.grp_nw8 = atoi(v) == 8;
+    return e;
+  }();
+  return env;
+}
 
 // the FAST preconditions on the data path (the kernels' compile-time configuration): the
 // SAMPLER_TABLE ring, the dataset cached in LDS, 0 <= slope <= 1, batch <= kBlock.  The
 // several-lanes and split-batch steps need these, for every loss and optimizer they serve.
 bool fast_base_ok(const DtpTrainArgs& a, int in, int out) {
-  static const bool disabled = [] {
-    const char* e = getenv("DTP_FAST");
-    return e && e[0] == '0';
-  }();
-  if (disabled) return false;
+  if (step_env().no_fast) return false;
   const dtp::SamplerCfg& s = a.smp;
   const int ydim = a.loss == DTP_LOSS_CE ? 1 : out;
   // n >= world: the FAST gather wraps a padded-list position with ONE subtraction of n
@@ -55,10 +83,13 @@ bool fast_path_ok(const DtpTrainArgs& a, int in, int out, int mode) {
          a.loss == DTP_LOSS_MSE;
 }
 
-// the step instance of a launch: lanes per sample and waves per workgroup
-struct LanePick {
-  int L = 1, NW = 4;
-  int GR = 1;  // workgroups per model (split-batch step, grp_core.h)
+// The step instance of a launch: its launcher (null: no instance serves the launch), lanes
+// per sample (1: the one-lane kernel), waves per workgroup, workgroups per model (> 1: the
+// split-batch step, grp_core.h) and variant.
+struct StepPick {
+  TrainLaunchFn fn = nullptr;
+  int L = 1, NW = 4, GR = 1;
+  StepVariant v = kPlain;
 };
 
 // threads of the workgroups the fused step instances launch (one-lane: kBlock; lanes:
@@ -75,57 +106,28 @@ int xgmi_max_slot16(int P) {
   return m;
 }
 
-// does the launch clip its gradient in the kernel (a clip twin, clip_core.h)?
+// does the launch clip its gradient in the kernel (clip_core.h)?
 bool clip_set(const DtpTrainArgs& a) { return a.max_norm > 0.f || a.clip_value > 0.f; }
 
-// does the launch run an accumulation twin (accum_core.h)?  DTP_ACCUM_TWIN=1 (read once, for
-// tests and A/B runs) sends a launch without accumulation to the twin too: one micro-batch per step
-bool accum_set(const DtpTrainArgs& a) {
-  static const bool forced = [] {
-    const char* e = getenv("DTP_ACCUM_TWIN");
-    return e && e[0] == '1';
-  }();
-  return a.accum > 1 || forced;
+// does the launch ask for an accumulation twin (accum_core.h)?  Under DTP_ACCUM_TWIN=1 a launch
+// without accumulation does too: one micro-batch per step
+bool accum_set(const DtpTrainArgs& a) { return a.accum > 1 || step_env().accum_twin; }
+
+// The variant of a launch, decided here only: an accumulating launch of an update mode runs
+// the accumulation twin (which clips at run time), any other clipping launch the clip twin.
+StepVariant step_variant(const DtpTrainArgs& a, int mode) {
+  if (accum_set(a) && mode != DTP_MODE_GRAD) return kAccum;
+  return clip_set(a) ? kClip : kPlain;
 }
 
-// DTP_LANES=<L>[x<NW>] as given (L = 0: unset)
-const LanePick& forced_lanes_env() {
-  static const LanePick forced = [] {
-    LanePick f{0, 4};
-    const char* e = getenv("DTP_LANES");
-    if (e) {
-      f.L = atoi(e);
-      const char* x = strchr(e, 'x');
-      if (x) f.NW = atoi(x + 1);
-    }
-    return f;
-  }();
-  return forced;
-}
-// the 8-wave instances have no clip twin and no accumulation twin: a clipping or accumulating
-// launch resolves as if DTP_LANES=..x8 had not been given
-bool forced_lanes_ignored(const DtpTrainArgs& a, int mode = DTP_MODE_ADAM) {
-  return (clip_set(a) || (accum_set(a) && mode != DTP_MODE_GRAD)) && forced_lanes_env().NW == 8;
-}
-
-// 4 lanes per sample for per-rank batches <= 64, 2 for <= 128, else the one-lane kernel
-// (L = 1).  DTP_LANES=<L>[x<NW>] forces a choice (A/B runs; NW = 8 runs two waves per
-// SIMD, 512 / L samples); a forced pick whose batch bound does not hold falls back to 1.
 // Split-batch step (engine launches only: it owns the exchange buffer): a per-rank batch
 // above 64 on one rank runs on ceil(batch / 64) workgroups per model, each the 4-lanes step
-// on 64 samples, their gradients summed on chip.  DTP_GROUPS=1 turns it off (A/B runs).
-// DTP_GROUPS: unset = the measured policy below, "on" = wherever an instance exists,
-// "off" / "0" / "1" = never (A/B runs)
-int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow, int mode) {
-  static const int env = [] {  // -1 policy, 0 off, 1 on
-    const char* e = getenv("DTP_GROUPS");
-    if (!e) return -1;
-    return strcmp(e, "on") == 0 ? 1 : 0;
-  }();
-  // a forced lanes instance runs as asked
-  const bool forced_lanes = getenv("DTP_LANES") != nullptr && !forced_lanes_ignored(a, mode);
+// on 64 samples, their gradients summed on chip.  DTP_GROUPS (StepEnv) overrides the caller's
+// request; a forced lanes instance (DTP_LANES) runs as asked.
+int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow, bool forced_lanes) {
   // the caller's request (DtpTrainArgs.groups before the engine fills it in): 0 policy,
   // 1 on, -1 off; the environment wins (A/B runs)
+  const int env = step_env().groups;
   const int want = env >= 0 ? env : (a.groups > 0 ? 1 : (a.groups < 0 ? 0 : -1));
   if (!allow || want == 0 || forced_lanes || a.n_models > 8) return 1;
   if (a.smp.n * (in + out) > dtp::kLaneData) return 1;
@@ -144,100 +146,82 @@ int pick_groups(const DtpTrainArgs& a, int in, int out, bool allow, int mode) {
   return gr >= 4 ? gr : 1;
 }
 
-LanePick pick_lanes(const DtpTrainArgs& a, int in, int out, bool fast, int mode) {
-  const LanePick forced = forced_lanes_ignored(a, mode) ? LanePick{0, 4} : forced_lanes_env();
-  LanePick r;
+// 4 lanes per sample for per-rank batches <= 64, 2 for <= 128, else the one-lane kernel
+// (L = 1).  DTP_LANES=<L>[x<NW>] forces a choice (A/B runs; NW = 8 runs two waves per
+// SIMD, 512 / L samples); a forced pick whose batch bound does not hold falls back to 1.
+StepPick pick_lanes(const DtpTrainArgs& a, int in, int out, bool fast, bool forced_lanes) {
+  const StepEnv& env = step_env();
+  StepPick r;
   if (!fast || a.smp.n * (in + out) > dtp::kLaneData) return r;
   // the largest batch a step sees: a rank's share of the epoch can be smaller than the
   // configured batch (strong scaling: 512 samples over 8 ranks -> 64 of batch 256)
   const int b = min(a.smp.batch, a.smp.num_samples);
   r.L = b <= dtp::kBlock / 4 ? 4 : (b <= dtp::kBlock / 2 ? 2 : 1);
-  if ((forced.L == 1 || forced.L == 2 || forced.L == 4) && (forced.NW == 4 || forced.NW == 8)) {
-    r.L = forced.L;
-    r.NW = forced.L == 1 ? 4 : forced.NW;
+  if (forced_lanes && (env.L == 1 || env.L == 2 || env.L == 4) && (env.NW == 4 || env.NW == 8)) {
+    r.L = env.L;
+    r.NW = env.L == 1 ? 4 : env.NW;
   }
-  if (b > 64 * r.NW / r.L) r = LanePick{};
+  if (b > 64 * r.NW / r.L) r = StepPick{};
   return r;
 }
 
-TrainLaunchFn resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int out, int mode,
-                            LanePick* pick = nullptr, bool allow_groups = false, bool* no_twin = nullptr) {
+// The step a validated launch takes.  The candidates, in order: the split-batch step, the
+// lanes step, the one-lane kernel; the first with an instance in the launch's variant wins.
+// A pick without a twin (the 8-wave instances, FAST one-lane; for accumulation every one-lane
+// instance) is a null entry of that variant's row: the next candidate is tried, and a launch
+// left with none returns fn = null.
+StepPick resolve_train(const DtpTrainArgs& a, int in, int h, int nl, int out, int mode, bool allow_groups = false) {
+  const StepEnv& env = step_env();
+  const StepVariant v = step_variant(a, mode);
   const bool base = fast_base_ok(a, in, out);
-  const bool fast = fast_path_ok(a, in, out, mode);
-  const bool ce = a.loss == DTP_LOSS_CE;
-  // a clipping launch (max_norm / clip_value set): the unclipped launch's pick, then its clip
-  // twin; where the pick has no twin (the 8-wave instances, FAST one-lane) the next candidate
-  // in the same order, down to the generic one-lane twin, which every supported shape has
-  const bool clip = clip_set(a);
-  // an accumulating launch (accum > 1, or DTP_ACCUM_TWIN): the plain launch's pick, then its
-  // accumulation twin, which clips at run time.  A pick without a twin (the one-lane kernel,
-  // an 8-wave instance) is an error, never a plain step: *no_twin names it.
-  const bool accum = accum_set(a) && mode != DTP_MODE_GRAD;
-  LanePick lp = pick_lanes(a, in, out, base, mode);
-  const LanesInst* li = base ? dtp::lanes_inst(in, h, nl, out, a.bf16, ce, mode) : nullptr;
-  if (li) {
-    const int gr = pick_groups(a, in, out, allow_groups, mode);
+  const int x = dtp::mode_xgmi(mode);
+  // the 8-wave instances have no twins: a clipping or accumulating launch resolves as if
+  // DTP_LANES=..x8 had not been given
+  const bool forced_lanes = env.lanes_set && !(v != kPlain && env.NW == 8);
+  if (const LanesInst* li = base ? dtp::lanes_inst(in, h, nl, out, a.bf16, a.loss == DTP_LOSS_CE, mode) : nullptr) {
+    const int gr = pick_groups(a, in, out, allow_groups, forced_lanes);
     // A/B only (DTP_GRP_NW=8): the split-batch step on members of 128 samples, each the
     // two-waves-per-SIMD 4-lanes step (8 waves), half the members of the default -- toy
     // fp32 Adam + MSE at one rank (docs/perf_notes.md "Round 6: two members")
-    static const bool nw8 = getenv("DTP_GRP_NW") && atoi(getenv("DTP_GRP_NW")) == 8;
-    if (nw8 && !clip && !accum && gr > 1 && mode == DTP_MODE_ADAM && li->grp8) {
-      const int b = min(a.smp.batch, a.smp.num_samples);
-      const int gr8 = (b + 127) / 128;
-      if (gr8 > 1 && a.smp.n * (in + out) <= dtp::kLaneData) {
-        if (pick) *pick = LanePick{4, 8, gr8};
-        return li->grp8;
-      }
+    if (env.grp_nw8 && v == kPlain && gr > 1 && mode == DTP_MODE_ADAM && li->grp8) {
+      const int gr8 = (min(a.smp.batch, a.smp.num_samples) + 127) / 128;
+      if (gr8 > 1 && a.smp.n * (in + out) <= dtp::kLaneData) return StepPick{li->grp8, 4, 8, gr8, v};
     }
-    if (gr > 1) {
-      if (TrainLaunchFn f = (accum ? li->accum_grp : clip ? li->clip_grp : li->grp)[dtp::mode_xgmi(mode) ? 2 : (gr == 4 ? 1 : 0)]) {
-        if (pick) *pick = LanePick{4, 4, gr};
-        return f;
-      }
-    }
-    if (lp.L > 1) {
-      TrainLaunchFn f = li->lanes[lp.NW == 8][lp.L == 4][dtp::mode_xgmi(mode)];
-      if (clip) f = lp.NW == 4 ? li->clip_lanes[lp.L == 4][dtp::mode_xgmi(mode)] : nullptr;
-      if (accum) f = lp.NW == 4 ? li->accum_lanes[lp.L == 4][dtp::mode_xgmi(mode)] : nullptr;
-      if (f) {
-        if (pick) *pick = lp;
-        return f;
-      }
-    }
+    if (gr > 1)
+      if (TrainLaunchFn f = li->grp[v][x ? 2 : (gr == 4 ? 1 : 0)]) return StepPick{f, 4, 4, gr, v};
+    const StepPick lp = pick_lanes(a, in, out, base, forced_lanes);
+    if (lp.L > 1)
+      if (TrainLaunchFn f = li->lanes[v][lp.NW == 8][lp.L == 4][x]) return StepPick{f, lp.L, lp.NW, 1, v};
   }
-  if (pick) *pick = LanePick{};
-  if (accum) {
-    if (no_twin) *no_twin = true;
-    return nullptr;
-  }
-  const dtp::OneInst* oi = dtp::one_lane_inst(in, h, nl, out, a.bf16);
-  if (!oi || mode < DTP_MODE_GRAD || mode > DTP_MODE_XGMI_SGD) return nullptr;
-  if (clip) return oi->clip[mode];
-  return fast && oi->fast[mode] ? oi->fast[mode] : oi->fn[mode];
+  StepPick one;
+  one.v = v;
+  if (const dtp::OneInst* oi = dtp::one_lane_inst(in, h, nl, out, a.bf16))
+    one.fn = v == kPlain && fast_path_ok(a, in, out, mode) && oi->fast[mode] ? oi->fast[mode] : oi->fn[v][mode];
+  return one;
 }
 
-// the xGMI receive buffer covers the picked instance's granule layout (peers' stores
-// through a buffer resource are not bounds-checked: an undersized buffer is corrupted)
-int check_xbuf(const DtpTrainArgs& a, int in, int h, int nl, int out, int mode, const LanePick& lp) {
+// What stands between a pick and its launch, as the error it leaves (0: none).  No instance:
+// -6 for an accumulating launch (its pick has no accumulation twin), else -2.  And the xGMI
+// receive buffer must cover the picked instance's granule layout (peers' stores through a
+// buffer resource are not bounds-checked: an undersized buffer is corrupted).
+int pick_err(const DtpTrainArgs& a, int in, int h, int nl, int out, int mode, const StepPick& p) {
+  char m[288];
+  if (!p.fn && p.v == kAccum) {
+    snprintf(m, sizeof m, "gradient accumulation (accum = %d): this launch picks a step instance without an "
+             "accumulation twin (the one-lane kernel: a per-rank batch above 128 without the split-batch step, "
+             "groups off, or a shape / data path the several-lanes step does not serve)", a.accum);
+    return set_err(-6, m);
+  }
+  if (!p.fn) return set_err(-2, "mlp shape / mode not instantiated for the fused train kernel");
   if (!dtp::mode_xgmi(mode) || a.xbuf_bytes <= 0) return 0;
   const int P = dtp_mlp_param_count(in, h, nl, out);
-  const int nth = lp.L > 1 ? 64 * lp.NW : dtp::kBlock;
-  const long long need = xgmi_bytes_for(a.n_models, a.smp.world * lp.GR, xgmi_slot16_threads(P, nth));
+  const int nth = p.L > 1 ? 64 * p.NW : dtp::kBlock;
+  const long long need = xgmi_bytes_for(a.n_models, a.smp.world * p.GR, xgmi_slot16_threads(P, nth));
   if (need > a.xbuf_bytes) {
-    char m[160];
     snprintf(m, sizeof m, "xGMI receive buffer too small: %lld bytes needed, %d allocated", need, a.xbuf_bytes);
     return set_err(-5, m);
   }
   return 0;
-}
-
-// an accumulating launch whose pick has no accumulation twin
-int no_twin_err(const DtpTrainArgs& a) {
-  char m[224];
-  snprintf(m, sizeof m, "gradient accumulation (accum = %d): this launch picks a step instance without an "
-           "accumulation twin (the one-lane kernel: a per-rank batch above 128 without the split-batch step, "
-           "groups off, or a shape / data path the several-lanes step does not serve)", a.accum);
-  return set_err(-6, m);
 }
 
 int validate_train(const DtpTrainArgs* a, int mode) {
@@ -288,9 +272,8 @@ int validate_train(const DtpTrainArgs* a, int mode) {
 // dispatch on the host; the Python side calls it with (handle, n_steps, stream)).
 struct TrainEngine {
   DtpTrainArgs a;
-  TrainLaunchFn fn;
   int mode;
-  LanePick pick;  // lanes per sample / waves of the chosen instance (L = 1: mlp_train_kernel)
+  StepPick pick;  // the instance it launches
   void* grp_mem = nullptr;  // split-batch step: [status 16 ints | epochs | granule buffer]
   ~TrainEngine() {
     if (grp_mem) (void)hipFree(grp_mem);
@@ -365,33 +348,21 @@ int dtp_mlp_train(const DtpTrainArgs* a, int in, int h, int nl, int out, int mod
   if (int rc = validate_train(a, mode)) return rc;
   if (mode == DTP_MODE_GRAD && a->n_steps != 1) return set_err(-4, "MODE_GRAD requires n_steps == 1");
   if (int rc = check_sched_t0(*a, mode, a->host_t0)) return rc;
-  LanePick lp;
-  bool no_twin = false;
-  TrainLaunchFn fn = resolve_train(*a, in, h, nl, out, mode, &lp, false, &no_twin);
-  if (!fn && no_twin) return no_twin_err(*a);
-  if (!fn) return set_err(-2, "mlp shape / mode not instantiated for the fused train kernel");
-  if (int rc = check_xbuf(*a, in, h, nl, out, mode, lp)) return rc;
-  fn(*a, (hipStream_t)stream);
+  const StepPick p = resolve_train(*a, in, h, nl, out, mode);
+  if (int rc = pick_err(*a, in, h, nl, out, mode, p)) return rc;
+  p.fn(*a, (hipStream_t)stream);
   return check_launch("mlp_train_kernel");
 }
 
 void* dtp_train_engine_create(const DtpTrainArgs* a, int in, int h, int nl, int out, int mode) {
   if (validate_train(a, mode)) return nullptr;
-  LanePick lp;
-  bool no_twin = false;
-  TrainLaunchFn fn = resolve_train(*a, in, h, nl, out, mode, &lp, true, &no_twin);
-  if (!fn) {
-    if (no_twin) no_twin_err(*a);
-    else set_err(-2, "mlp shape / mode not instantiated for the fused train kernel");
-    return nullptr;
-  }
-  if (check_xbuf(*a, in, h, nl, out, mode, lp)) return nullptr;
+  const StepPick p = resolve_train(*a, in, h, nl, out, mode, true);
+  if (pick_err(*a, in, h, nl, out, mode, p)) return nullptr;
   auto* e = new TrainEngine();
   e->a = *a;
-  e->fn = fn;
   e->mode = mode;
-  e->pick = lp;
-  if (lp.GR > 1 && grp_alloc(e, dtp_mlp_param_count(in, h, nl, out))) {
+  e->pick = p;
+  if (p.GR > 1 && grp_alloc(e, dtp_mlp_param_count(in, h, nl, out))) {
     delete e;
     return nullptr;
   }
@@ -419,12 +390,6 @@ int dtp_train_engine_profile(void* h, int n_steps, int t0, void* prof, void* str
   return check_launch("mlp_train_lanes_kernel<grp, prof>");
 }
 
-// workgroups per model of the engine's step (1, or the split-batch step's group size)
-int dtp_train_engine_groups(void* h) {
-  auto* e = static_cast<TrainEngine*>(h);
-  return e ? e->pick.GR : set_err(-1, "null engine");
-}
-
 // the split-batch exchange's sticky timeout words {flag, epoch} (synchronous copy; 0/0
 // when the engine has no split-batch step)
 int dtp_train_engine_status(void* h, int* out2) {
@@ -448,30 +413,24 @@ int dtp_train_engine_poison(void* h, int epoch) {
   return 0;
 }
 
-// 1 when the engine's step is a clip twin (clip_core.h): it clips the gradient in the kernel
-int dtp_train_engine_clip(void* h) {
+// the step the engine runs
+int dtp_train_engine_pick(void* h, DtpStepPick* out) {
   auto* e = static_cast<TrainEngine*>(h);
-  return e ? (clip_set(e->a) ? 1 : 0) : set_err(-1, "null engine");
+  if (!e || !out) return set_err(-1, "null engine");
+  *out = DtpStepPick{e->pick.L, e->pick.NW, e->pick.GR, e->pick.v};
+  return 0;
 }
 
-// 1 when the engine's step is an accumulation twin (accum_core.h)
-int dtp_train_engine_accum(void* h) {
-  auto* e = static_cast<TrainEngine*>(h);
-  return e ? (accum_set(e->a) && e->mode != DTP_MODE_GRAD ? 1 : 0) : set_err(-1, "null engine");
-}
-
-// lanes per sample of the engine's kernel instance (1 = one lane per sample)
-int dtp_train_engine_lanes(void* h) {
-  auto* e = static_cast<TrainEngine*>(h);
-  return e ? e->pick.L : set_err(-1, "null engine");
-}
-
-// lanes per sample (low byte), waves per workgroup (<< 8) and workgroups per model (<< 16)
-// of the step a train engine would launch for these arguments (0: no fused instance)
-int dtp_mlp_train_lanes(const DtpTrainArgs* a, int in, int h, int nl, int out, int mode) {
-  if (validate_train(a, mode)) return 0;
-  LanePick lp;
-  return resolve_train(*a, in, h, nl, out, mode, &lp, true) ? (lp.L | (lp.NW << 8) | (lp.GR << 16)) : 0;
+// the step a train engine would run for these arguments: validation and the engine's pick.
+// 0, or the error dtp_train_engine_create would leave, with *out zeroed
+int dtp_mlp_train_pick(const DtpTrainArgs* a, int in, int h, int nl, int out, int mode, DtpStepPick* pick) {
+  if (!pick) return set_err(-1, "null pick record");
+  *pick = DtpStepPick{};
+  if (int rc = validate_train(a, mode)) return rc;
+  const StepPick p = resolve_train(*a, in, h, nl, out, mode, true);
+  if (int rc = pick_err(*a, in, h, nl, out, mode, p)) return rc;
+  *pick = DtpStepPick{p.L, p.NW, p.GR, p.v};
+  return 0;
 }
 
 // n_steps iterations in ONE persistent launch on `stream`, starting at step t0 (the
@@ -486,7 +445,7 @@ int dtp_train_engine_run(void* h, int n_steps, int t0, void* stream) {
     return set_err(-4, "accumulation: t0 * accum and n_steps * accum must stay below 2^31");
   e->a.n_steps = n_steps;
   e->a.host_t0 = t0;
-  e->fn(e->a, (hipStream_t)stream);
+  e->pick.fn(e->a, (hipStream_t)stream);
   return check_launch("mlp_train_kernel");
 }
 

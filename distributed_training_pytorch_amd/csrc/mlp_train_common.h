@@ -1,7 +1,8 @@
-// What the fused train step's three sources share (mlp_train.hip: host dispatch, engine and
-// C API; mlp_train_one.hip: the one-lane kernel; mlp_train_lanes.hip: the several-lanes /
-// split-batch kernel): the LDS budgets the host's picks test, the Adam-table helpers, the
-// PROF stamp, and the instance tables' entry types with their two lookups.
+// What the fused train step's sources share (mlp_train.hip: host dispatch, engine and C API;
+// mlp_train_one.hip: the one-lane kernel; mlp_train_lanes.hip and its two twin sources: the
+// several-lanes / split-batch kernel, mlp_train_lanes_kernel.h): the LDS budgets the host's
+// picks test, the Adam-table helpers, the PROF stamp, and the instance tables' entry types with
+// their two lookups.
 #pragma once
 #include "dtp_api.h"
 #include "mlp_core.h"
@@ -61,15 +62,19 @@ using TrainLaunchFn = void (*)(const DtpTrainArgs&, hipStream_t);
 constexpr bool mode_sgd(int mode) { return mode == DTP_MODE_SGD || mode == DTP_MODE_XGMI_SGD; }
 constexpr bool mode_xgmi(int mode) { return mode == DTP_MODE_XGMI_ADAM || mode == DTP_MODE_XGMI_SGD; }
 
+// The variant of a step instance: the plain step, its clip twin (clip_core.h: MODE | kModeClip)
+// or its accumulation twin (accum_core.h: MODE | kModeAccum, which clips at run time).  A
+// dimension of both instance tables; an instance without such a twin has a null entry there.
+enum StepVariant { kPlain, kClip, kAccum, kVariants };
+
 // One row of the one-lane table (mlp_train_one.hip): a (shape, precision) and its launchers.
 struct OneInst {
   int in, h, nl, out;
   bool bf16;
-  int ws;                // Scal<S>::WS, floats of workspace
-  TrainLaunchFn fn[5];   // by DtpMode
-  TrainLaunchFn fast[5]; // the FAST instance of the mode (the Adam modes), else null
-  TrainLaunchFn prof;    // PROF instance (FAST Adam), or null
-  TrainLaunchFn clip[5]; // the clip twin of the generic instance (clip_core.h), the four update modes
+  int ws;                          // Scal<S>::WS, floats of workspace
+  TrainLaunchFn fn[kVariants][5];  // by DtpMode; clip twins: the four update modes; no accumulation twins
+  TrainLaunchFn fast[5];           // the FAST instance of the mode (the Adam modes, plain only), else null
+  TrainLaunchFn prof;              // PROF instance (FAST Adam), or null
 };
 const OneInst* one_lane_inst(int in, int h, int nl, int out, bool bf16);
 
@@ -78,17 +83,11 @@ const OneInst* one_lane_inst(int in, int h, int nl, int out, bool bf16);
 struct LanesInst {
   int in, h, nl, out;
   bool bf16, ce, sgd;
-  TrainLaunchFn lanes[2][2][2];  // [8 waves][L == 4 (else 2)][xGMI]
-  TrainLaunchFn grp[3];          // split-batch: run-time member count, 4 members, xGMI
-  TrainLaunchFn grp8;            // split-batch on 8-wave members (DTP_GRP_NW=8 A/B)
-  TrainLaunchFn prof[2][2];      // PROF lanes instances [8 waves][L == 4]
-  TrainLaunchFn grp_prof[2];     // PROF split-batch instances [4 members as a constant]
-  // the clip twins (clip_core.h) of the 4-wave instances; none of the 8-wave, grp8 and PROF ones
-  TrainLaunchFn clip_lanes[2][2];  // [L == 4 (else 2)][xGMI]
-  TrainLaunchFn clip_grp[3];       // as grp
-  // the accumulation twins (accum_core.h) of the same instances; they clip at run time
-  TrainLaunchFn accum_lanes[2][2];  // [L == 4 (else 2)][xGMI]
-  TrainLaunchFn accum_grp[3];       // as grp
+  TrainLaunchFn lanes[kVariants][2][2][2];  // [variant][8 waves][L == 4 (else 2)][xGMI]; the twins: 4 waves only
+  TrainLaunchFn grp[kVariants][3];          // split-batch: run-time member count, 4 members, xGMI
+  TrainLaunchFn grp8;                       // split-batch on 8-wave members (DTP_GRP_NW=8 A/B)
+  TrainLaunchFn prof[2][2];                 // PROF lanes instances [8 waves][L == 4]
+  TrainLaunchFn grp_prof[2];                // PROF split-batch instances [4 members as a constant]
 };
 // the family that serves `mode` (an optimizer mode), or null
 const LanesInst* lanes_inst(int in, int h, int nl, int out, bool bf16, bool ce, int mode);

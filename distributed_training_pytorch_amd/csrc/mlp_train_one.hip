@@ -463,7 +463,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
 // The instance table.  (IN, H, NL, OUT, bf16 compute, PROF): every row has all five modes
 // plus the FAST instance of the two Adam modes (the training configuration of the demos and
 // bench.py), and the clip twin of the generic instance in the four update modes (a clipped
-// launch has no FAST instance: it runs the generic twin).
+// launch has no FAST instance: it runs the generic twin).  No accumulation twins: that row of
+// OneInst.fn stays null.
 #define DTP_ONE_SHAPES(X)                                                        \
   X(2, 10, 5, 1, false, true)  /* the toy model; the phase-stamp diagnostic */   \
   X(2, 10, 5, 1, true, false)                                                    \
@@ -477,19 +478,25 @@ void launch_one(const DtpTrainArgs& a, hipStream_t st) {
   hipLaunchKernelGGL((mlp_train_kernel<S, MODE, PROF, FAST>), dim3(a.n_models), dim3(kBlock), 0, st, a);
 }
 
+// variant V (plain or clip twin: MODE carries the variant's bit) of a row's four update modes
+template <class S, StepVariant V>
+constexpr void one_fill(OneInst& r) {
+  constexpr int BIT = V == kClip ? kModeClip : 0;
+  r.fn[V][DTP_MODE_ADAM] = &launch_one<S, DTP_MODE_ADAM | BIT>;
+  r.fn[V][DTP_MODE_SGD] = &launch_one<S, DTP_MODE_SGD | BIT>;
+  r.fn[V][DTP_MODE_XGMI_ADAM] = &launch_one<S, DTP_MODE_XGMI_ADAM | BIT>;
+  r.fn[V][DTP_MODE_XGMI_SGD] = &launch_one<S, DTP_MODE_XGMI_SGD | BIT>;
+}
+
 template <class S, bool PROF>
 constexpr OneInst one_row() {
-  OneInst r{S::IN, S::H, S::NL, S::OUT, S::BF, Scal<S>::WS,
-            {&launch_one<S, DTP_MODE_GRAD>, &launch_one<S, DTP_MODE_ADAM>, &launch_one<S, DTP_MODE_SGD>,
-             &launch_one<S, DTP_MODE_XGMI_ADAM>, &launch_one<S, DTP_MODE_XGMI_SGD>},
-            {nullptr, &launch_one<S, DTP_MODE_ADAM, false, true>, nullptr,
-             &launch_one<S, DTP_MODE_XGMI_ADAM, false, true>, nullptr},
-            nullptr};
+  OneInst r{S::IN, S::H, S::NL, S::OUT, S::BF, Scal<S>::WS};
+  r.fn[kPlain][DTP_MODE_GRAD] = &launch_one<S, DTP_MODE_GRAD>;
+  one_fill<S, kPlain>(r);
+  one_fill<S, kClip>(r);
+  r.fast[DTP_MODE_ADAM] = &launch_one<S, DTP_MODE_ADAM, false, true>;
+  r.fast[DTP_MODE_XGMI_ADAM] = &launch_one<S, DTP_MODE_XGMI_ADAM, false, true>;
   if constexpr (PROF) r.prof = &launch_one<S, DTP_MODE_ADAM, true, true>;
-  r.clip[DTP_MODE_ADAM] = &launch_one<S, DTP_MODE_ADAM | kModeClip>;
-  r.clip[DTP_MODE_SGD] = &launch_one<S, DTP_MODE_SGD | kModeClip>;
-  r.clip[DTP_MODE_XGMI_ADAM] = &launch_one<S, DTP_MODE_XGMI_ADAM | kModeClip>;
-  r.clip[DTP_MODE_XGMI_SGD] = &launch_one<S, DTP_MODE_XGMI_SGD | kModeClip>;
   return r;
 }
 

@@ -108,6 +108,7 @@ class FusedTrainer:
         self._idx_stream = EpochIndexStream(geom)
         self._graphs: dict = {}
         self._engine = None  # native step executor (csrc/mlp_train.hip: dtp_train_engine_*)
+        self._pick_cache = None  # (groups_refused, StepPick) of _pick()
         self._fast = None  # (run, engine, device, max steps, ring, steps/epoch): train()'s direct path
         self._dev_index = self.device.index if self.device.index is not None else (
             torch.cuda.current_device() if self.device.type == "cuda" else -1)
@@ -167,20 +168,20 @@ class FusedTrainer:
         one-lane kernel, 2 / 4 = the several-lanes step (``csrc/mlp_lanes.h``) that the
         native dispatch picks for per-rank batches <= 128 / <= 64 (0: no fused kernel,
         e.g. a CPU engine or the RCCL path's grad kernel)."""
-        return self._pick() & 0xFF
+        return self._pick().lanes
 
     @property
     def kernel_waves(self) -> int:
         """Waves per workgroup of the fused step instance (4: one per SIMD; 8: two, the
         several-lanes step over 512 / L samples); 0 without a fused kernel."""
-        return (self._pick() >> 8) & 0xFF
+        return self._pick().waves
 
     @property
     def groups(self) -> int:
         """Workgroups per model of the persistent step: > 1 is the split-batch step
         (``csrc/grp_core.h``: a rank's batch over several CUs per model, 64 samples each,
         their gradients summed on chip); 1 otherwise, 0 without a fused kernel."""
-        return self._pick() >> 16
+        return self._pick().groups
 
     @property
     def clip_in_kernel(self) -> bool:
@@ -188,9 +189,7 @@ class FusedTrainer:
         instance, ``csrc/clip_core.h``)?  True for a clipping ``OptimConfig`` on the native
         single-kernel paths (``comm`` none / xgmi); the RCCL / host path and the CPU reference
         clip in ``flat_optimizer_step``."""
-        if not self.optim.clips or not self.native or self.comm in ("rccl", "host"):
-            return False
-        return bool(nat.load().dtp_train_engine_clip(self._engine_handle()))
+        return self.optim.clips and self._pick().variant != 0  # the accumulation twin clips too
 
     @property
     def accum_in_kernel(self) -> bool:
@@ -198,21 +197,26 @@ class FusedTrainer:
         accumulation twin of the step instance, ``csrc/accum_core.h``)?  True for
         ``accumulate > 1`` on the native single-kernel paths (``comm`` none / xgmi); the RCCL /
         host path and the CPU reference sum ``accumulate`` gradient evaluations instead."""
-        if not self.native or self.comm in ("rccl", "host"):
-            return False
-        return bool(nat.load().dtp_train_engine_accum(self._engine_handle()))
+        return self._pick().variant == 2
 
     def micro_batches(self, t: int) -> range:
         """The micro-batches optimizer step ``t`` consumes: arguments of :meth:`step_indices`."""
         return range(t * self.A, t * self.A + self.A)
 
-    def _pick(self) -> int:
-        if not self.native or self.comm in ("rccl", "host"):
-            return 0
-        a = self._train_args(1, self._update_mode(), None)
-        if self.groups_refused:
-            a.groups = -1
-        return int(nat.load().dtp_mlp_train_lanes(ctypes.byref(a), *self.spec.key[:4], self._update_mode()))
+    def _pick(self) -> nat.StepPick:
+        """The step the native dispatch picks for this engine's launches (``dtp_mlp_train_pick``: no
+        engine is created); all zeros without a native single-kernel path.  Kept until
+        :meth:`_drop_engine` or until ``groups_refused`` changes."""
+        if self._pick_cache is None or self._pick_cache[0] != self.groups_refused:
+            rec = nat.StepPick()
+            if self.native and self.comm not in ("rccl", "host"):
+                mode = self._update_mode()
+                a = self._train_args(1, mode, None)
+                if self.groups_refused:
+                    a.groups = -1
+                nat.load().dtp_mlp_train_pick(ctypes.byref(a), *self.spec.key[:4], mode, ctypes.byref(rec))
+            self._pick_cache = (self.groups_refused, rec)
+        return self._pick_cache[1]
 
     # ------------------------------------------------------------------ setup
     def _resolve_comm(self) -> str:
@@ -464,6 +468,7 @@ class FusedTrainer:
     def _drop_engine(self) -> None:
         """Destroy the native executor and every graph captured on it."""
         self._fast = None
+        self._pick_cache = None
         lib = nat.load() if self.native else None
         if self._engine is not None and lib is not None:
             lib.dtp_train_engine_destroy(self._engine)
@@ -484,7 +489,9 @@ class FusedTrainer:
             e = lib.dtp_train_engine_create(ctypes.byref(a), *self.spec.key[:4], mode)
             if not e:
                 nat.check(-1, "dtp_train_engine_create")
-            gr = lib.dtp_train_engine_groups(e)
+            rec = nat.StepPick()
+            nat.check(lib.dtp_train_engine_pick(e, ctypes.byref(rec)), "dtp_train_engine_pick")
+            gr = rec.groups
             cus = nat.masked_stream_cus.get(nat.raw_stream(self._dev_index))
             if gr > 1 and cus is not None and cus < 8 * gr:
                 # the split-batch members spin-wait on each other, so all 8 x groups

@@ -11,9 +11,9 @@ gradient read-out through the optimizer state are those of ``tests/step_cases.py
 gradient of each one's mean loss (a ragged batch divided by its own count), its logged loss the
 mean of their mean losses.
 
-**Twins.**  ``TWINS`` is written out from ``lanes_row()`` of ``csrc/mlp_train_lanes.hip``
-(``accum_lanes`` and ``accum_grp``, the local modes), NOT derived from the cells: 2 and 4 lanes of
-all eight families, and for the five split-batch families the run-time member count (``grp``) and
+**Twins.**  ``TWINS`` is written out from ``lanes_fill()`` of ``csrc/mlp_train_lanes_kernel.h``
+(the ``kAccum`` rows of ``LanesInst.lanes`` and ``LanesInst.grp``, the local modes), NOT derived
+from the cells: 2 and 4 lanes of all eight families, and for the five split-batch families the run-time member count (``grp``) and
 the constant 4 (``grp4``).
 
 **Geometries**, the smallest that reach each path and put a ragged batch and an epoch edge inside
@@ -69,9 +69,9 @@ def _twins():
     """(shape, lanes, waves, loss, optimizer, precision, kind) of every accumulation twin of the
     local update modes; kind: lanes, grp (run-time member count), grp4."""
     out = []
-    for L in (2, 4):  # LanesInst.accum_lanes[L][local]
+    for L in (2, 4):  # LanesInst.lanes[kAccum][4 waves][L][local]
         out += [(s, L, 4, lo, o, p, "lanes") for s, lo, o, p, _ in FAMILIES]
-    for kind in ("grp", "grp4"):  # LanesInst.accum_grp[0..1]
+    for kind in ("grp", "grp4"):  # LanesInst.grp[kAccum][0..1]
         out += [(s, 4, 4, lo, o, p, kind) for s, lo, o, p, g in FAMILIES if g]
     return out
 

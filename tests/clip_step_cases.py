@@ -7,8 +7,9 @@ whatever device they are given.  Cells, inputs and the gradient read-out through
 state are those of ``tests/step_cases.py``.
 
 **Twins.**  ``TWINS`` is written out from the tables of ``csrc/mlp_train_one.hip`` (one_row():
-the generic instance in the update modes) and ``csrc/mlp_train_lanes.hip`` (lanes_row():
-``clip_lanes`` and ``clip_grp``), NOT derived from the cells.  A twin's cell is the first cell of
+the generic instance in the update modes) and ``csrc/mlp_train_lanes_kernel.h`` (lanes_fill():
+the ``kClip`` rows of ``LanesInst.lanes`` and ``LanesInst.grp``), NOT derived from the cells.
+A twin's cell is the first cell of
 ``step_cases.CELLS`` that runs its plain instance; a FAST cell stands for the generic twin of
 its row (a clipped one-lane launch has no FAST instance).  The split-batch families have two
 local twins: the run-time member count (``grp``) and the constant 4 (``grp4``).
@@ -55,18 +56,18 @@ def _twins():
     """(shape, lanes, waves, loss, optimizer, precision, kind) of every clip twin of the local
     update modes; kind: generic (one lane), lanes, grp (run-time member count), grp4."""
     out = []
-    # DTP_ONE_SHAPES x OneInst.clip[ADAM, SGD]; the generic kernel takes the loss at run time
+    # DTP_ONE_SHAPES x OneInst.fn[kClip][ADAM, SGD]; the generic kernel takes the loss at run time
     for prec, shapes in (("fp32", ("T", "N3", "C4", "H15")), ("bf16", ("T", "C4"))):
         for s in shapes:
             out += [(s, 1, 4, "mse", "adam", prec, "generic"), (s, 1, 4, "mse", "sgd", prec, "generic")]
             if s == "C4":
                 out += [(s, 1, 4, "ce", "adam", prec, "generic"), (s, 1, 4, "ce", "sgd", prec, "generic")]
-    # DTP_LANES_FAMILIES x LanesInst.clip_lanes[L][local]: 4 waves only
+    # DTP_LANES_FAMILIES x LanesInst.lanes[kClip][4 waves][L][local]: 4 waves only
     for L in (2, 4):
         out += [(s, L, 4, "mse", "adam", "fp32", "lanes") for s in ("T", "N3", "C4", "H15")]
         out += [("T", L, 4, "mse", "sgd", "fp32", "lanes"), ("C4", L, 4, "ce", "adam", "fp32", "lanes"),
                 ("C4", L, 4, "ce", "sgd", "fp32", "lanes"), ("T", L, 4, "mse", "adam", "bf16", "lanes")]
-    # LanesInst.clip_grp[0..1] of the five split-batch families
+    # LanesInst.grp[kClip][0..1] of the five split-batch families
     for kind in ("grp", "grp4"):
         out += [("T", 4, 4, "mse", "adam", "fp32", kind), ("T", 4, 4, "mse", "sgd", "fp32", kind),
                 ("T", 4, 4, "mse", "adam", "bf16", kind), ("C4", 4, 4, "ce", "adam", "fp32", kind),

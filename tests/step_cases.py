@@ -307,7 +307,7 @@ def _xgmi_instances():
                     (s, 1, 4, "mse", "sgd", prec, "generic")]
             if s == "C4":
                 out += [(s, 1, 4, "ce", "adam", prec, "generic"), (s, 1, 4, "ce", "sgd", prec, "generic")]
-    # lanes_row(): every lanes instance has its xGMI twin
+    # lanes_fill() / lanes_row(): every lanes instance has its xGMI twin
     for L in (2, 4):
         out += [(s, L, 4, "mse", "adam", "fp32", "lanes") for s in ("T", "N3", "C4", "H15")]
         out += [("T", L, 4, "mse", "sgd", "fp32", "lanes"), ("C4", L, 4, "ce", "adam", "fp32", "lanes"),

@@ -289,6 +289,12 @@ def _last_error() -> str:
     return (nat.load().dtp_last_error() or b"").decode()
 
 
+def _engine_variant(lib, tr) -> int:
+    rec = nat.StepPick()
+    assert lib.dtp_train_engine_pick(tr._engine_handle(), ctypes.byref(rec)) == 0
+    return rec.variant
+
+
 def test_c_api_refusals():
     lib = nat.load()
     cell = ac.GRP4
@@ -300,7 +306,9 @@ def test_c_api_refusals():
         def refused(a, mode, word):
             rc = lib.dtp_mlp_train(ctypes.byref(a), *key, mode, nat.stream_ptr())
             assert rc != 0 and word in _last_error(), (rc, _last_error())
-            assert lib.dtp_mlp_train_lanes(ctypes.byref(a), *key, mode) == 0
+            rec = nat.StepPick(9, 9, 9, 9)
+            assert lib.dtp_mlp_train_pick(ctypes.byref(a), *key, mode, ctypes.byref(rec)) != 0
+            assert (rec.lanes, rec.waves, rec.groups, rec.variant) == (0, 0, 0, 0)
             assert not lib.dtp_train_engine_create(ctypes.byref(a), *key, mode)
 
         a = tr._train_args(1, nat.MODE_ADAM, None)
@@ -322,7 +330,7 @@ def test_c_api_refusals():
         assert lib.dtp_mlp_train_profile(ctypes.byref(a), nat.stream_ptr()) != 0 and "accumulation" in _last_error()
         assert lib.dtp_mlp_train_profile_lanes(ctypes.byref(a), 4, nat.stream_ptr()) != 0 and "accumulation" in _last_error()
         prof = torch.zeros(8 * 4 * 8 * 32, dtype=torch.int64, device=DEV)
-        assert lib.dtp_train_engine_accum(tr._engine_handle()) == 1
+        assert _engine_variant(lib, tr) == 2
         rc = lib.dtp_train_engine_profile(tr._engine_handle(), 1, 0, nat.ptr(prof), nat.stream_ptr())
         assert rc != 0 and "accumulation" in _last_error()
         # the direct launch has no split-batch step (it owns no exchange buffer): batch 256 picks
@@ -347,7 +355,7 @@ def test_c_api_refusals():
         off.close()
     plain = ac.make_trainer(cell, DEV, A=1)
     try:
-        assert lib.dtp_train_engine_accum(plain._engine_handle()) == 0 and not plain.accum_in_kernel
+        assert _engine_variant(lib, plain) == 0 and not plain.accum_in_kernel
     finally:
         plain.close()
 

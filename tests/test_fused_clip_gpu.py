@@ -151,6 +151,12 @@ def _last_error() -> str:
     return (nat.load().dtp_last_error() or b"").decode()
 
 
+def _engine_variant(lib, tr) -> int:
+    rec = nat.StepPick()
+    assert lib.dtp_train_engine_pick(tr._engine_handle(), ctypes.byref(rec)) == 0
+    return rec.variant
+
+
 def test_c_api_refusals_and_raw_local_gradients():
     lib = nat.load()
     cell = sc.BY_ID["T-adam-mse-fp32-b256-gon"]
@@ -163,7 +169,9 @@ def test_c_api_refusals_and_raw_local_gradients():
         def refused(a, mode):
             rc = lib.dtp_mlp_train(ctypes.byref(a), *key, mode, nat.stream_ptr())
             assert rc != 0 and "clipping" in _last_error(), (rc, _last_error())
-            assert lib.dtp_mlp_train_lanes(ctypes.byref(a), *key, mode) == 0
+            rec = nat.StepPick(9, 9, 9, 9)
+            assert lib.dtp_mlp_train_pick(ctypes.byref(a), *key, mode, ctypes.byref(rec)) != 0
+            assert (rec.lanes, rec.waves, rec.groups, rec.variant) == (0, 0, 0, 0)
             assert not lib.dtp_train_engine_create(ctypes.byref(a), *key, mode)
 
         before = [t.clone() for t in (tr.params, tr.m, tr.v, tr.step_ctr)]
@@ -190,8 +198,8 @@ def test_c_api_refusals_and_raw_local_gradients():
         for x, y in zip(before, (tr.params, tr.m, tr.v, tr.step_ctr)):
             assert torch.equal(x, y)
         # the clipping engine is a twin, the plain one is not; the profile instance has no twin
-        assert lib.dtp_train_engine_clip(tr._engine_handle()) == 1 and tr.clip_in_kernel
-        assert lib.dtp_train_engine_clip(plain._engine_handle()) == 0 and not plain.clip_in_kernel
+        assert _engine_variant(lib, tr) == 1 and tr.clip_in_kernel
+        assert _engine_variant(lib, plain) == 0 and not plain.clip_in_kernel
         prof = torch.zeros(8 * 4 * 8 * 32, dtype=torch.int64, device=DEV)
         rc = lib.dtp_train_engine_profile(tr._engine_handle(), 1, 0, nat.ptr(prof), nat.stream_ptr())
         assert rc != 0 and "clipping" in _last_error()

@@ -64,7 +64,8 @@ def test_build_flags_pin_fused_step_numerics():
     with the max-ILP scheduler; nothing else inherits those flags."""
     from distributed_training_pytorch_amd import build
 
-    for src in ("mlp_train.hip", "mlp_train_one.hip", "mlp_train_lanes.hip"):  # host side, the two kernels
+    for src in ("mlp_train.hip", "mlp_train_one.hip", "mlp_train_lanes.hip", "mlp_train_lanes_clip.hip",
+                "mlp_train_lanes_accum.hip"):  # host side, the two kernels, the lanes kernel's twins
         assert "-ffp-contract=off" in build.SOURCE_FLAGS[src]
         assert "-amdgpu-sched-strategy=max-ilp" in build.SOURCE_FLAGS[src]
     assert "-ffp-contract=off" in build.SOURCE_FLAGS["optim.hip"]
