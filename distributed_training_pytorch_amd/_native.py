@@ -322,7 +322,6 @@ def _declare(lib):
         "dtp_split_stage_supported": (c_int, [c_int] * 6),
         "dtp_split_link_bytes": (c_longlong, [c_int, c_int]),
         "dtp_split_lanes_launch": (c_int, [P(SplitLaunch), c_void_p]),
-        "dtp_split_lanes_supported": (c_int, [c_int] * 6),
         "dtp_split_lanes_grp_bytes": (c_longlong, [c_int, c_int]),
         "dtp_sampler_indices": (c_int, [P(SamplerCfg), c_longlong, c_int, c_void_p, c_void_p]),
         "dtp_get_device": (c_int, [P(c_int)]),

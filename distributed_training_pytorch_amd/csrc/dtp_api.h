@@ -207,7 +207,6 @@ long long dtp_split_link_bytes(int width, int batch);
 int dtp_split_stage_supported(int in, int h, int nl, int out, int final_act, int first);
 // split-batch stages: every stage's batch over L->members workgroups of the 4-lanes schedule
 int dtp_split_lanes_launch(const DtpSplitLaunch* L, void* stream);
-int dtp_split_lanes_supported(int in, int h, int nl, int out, int final_act, int first);
 long long dtp_split_lanes_grp_bytes(int P, int members);
 
 // ---- flat optimizers over [n_models][P] (after an external all-reduce) ----

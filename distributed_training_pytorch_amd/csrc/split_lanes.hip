@@ -34,12 +34,13 @@
 #include "mlp_lanes.h"
 #include "optim_core.h"
 #include "sampler.h"
+#include "split_core.h"
+#include "split_shapes.h"
 #include "xgmi_core.h"
 
 namespace dtp {
 
 constexpr int kSLData = 4096;     // floats of dataset staged in LDS (first: inputs, last: targets)
-constexpr int kSLAdamTab = 1024;  // Adam bias-correction scalars formed per this many steps
 constexpr int kSLMaxM = 8;        // members per stage
 
 // 4 lanes per sample, 4 waves of 16 samples: 64 samples per member
@@ -98,7 +99,7 @@ struct SLSmem {
   alignas(16) float wb[C::pad4(C::LW) + 4];          // weight blocks, then 4 sink floats
   alignas(16) float stg[C::NW][S::NL][2 * C::AREA];  // per wave, per layer: dz operand, h operand
   alignas(16) float red[C::NW][S::NL * C::TSZ];      // per-wave parked dW tiles
-  alignas(16) float2 adam_tab[kSLAdamTab];
+  alignas(16) float2 adam_tab[kSplitAdamTab];
   alignas(16) float data[kSLData];
   // member exchange (grp_allreduce_split3) or the cross-rank one (xgmi_allreduce_g3)
   static constexpr int XF = (kGrpMax + 1) * grp_ps3(S::P) > xgmi_g3_lds_floats(S::P)
@@ -144,7 +145,7 @@ DTP_DEV void sl_send(void* buf, int idx, unsigned ep, const float (&v)[3], bool 
   const u32x4 q = {ep ^ xgmi_hash3(x0, x1, x2), x0, x1, x2};
   const __amdgpu_buffer_rsrc_t rs = xgmi_rsrc(buf);
   if (local && plain) __builtin_amdgcn_raw_buffer_store_b128(q, rs, idx * 16, 0, 0);
-  else if (local) __builtin_amdgcn_raw_buffer_store_b128(q, rs, idx * 16, 0, 16);  // sc1: device scope
+  else if (local) __builtin_amdgcn_raw_buffer_store_b128(q, rs, idx * 16, 0, kDevCoherent);
   else __builtin_amdgcn_raw_buffer_store_b128(q, rs, idx * 16, 0, kSysCoherent);
 }
 
@@ -162,7 +163,7 @@ DTP_DEV void sl_recv(const void* buf, int idx, unsigned ep, float (&v)[3], bool 
   unsigned spins = 0;
   while (true) {
     asm volatile("" ::: "memory");  // a poll is never merged with or hoisted above the previous one
-    const u32x4 x = local ? __builtin_amdgcn_raw_buffer_load_b128(ms, idx * 16, 0, 16)
+    const u32x4 x = local ? __builtin_amdgcn_raw_buffer_load_b128(ms, idx * 16, 0, kDevCoherent)
                           : __builtin_amdgcn_raw_buffer_load_b128(ms, idx * 16, 0, kSysCoherent);
     if ((x.x ^ xgmi_hash3(x.y, x.z, x.w)) == ep) {
       v[0] = __uint_as_float(x.y);
@@ -286,7 +287,7 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
   static_for<0, S::IN>([&](auto IC) { nx[decltype(IC)::value] = 0.f; });
   static_for<0, S::OUT>([&](auto JC) { ny[decltype(JC)::value] = 0.f; });
   auto fill_adam = [&](int base) {
-    const int n = min(kSLAdamTab, a.n_steps - base);
+    const int n = min(kSplitAdamTab, a.n_steps - base);
     for (int e = tid; e < n; e += NTH) {
       const uint64_t t1 = (uint64_t)t0 + (uint64_t)base + (uint64_t)e + 1u;
       const double lr_t = lr_of(a.hp, (long long)t1 - 1);  // the rate after t1 - 1 taken steps
@@ -340,7 +341,6 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
   // a staging write with nothing to stage goes to row / column 15 of its sample slot (never
   // read): branch-free writes
   auto put = [&](float* tl, int off, bool ok, float v) { tl[ok ? off : wslot + 15 * TS] = v; };
-  float* const sink = sm.wb + C::pad4(C::LW);
 
   for (int it = 0; it < a.n_steps; ++it) {
     const int t = t0 + it;
@@ -551,7 +551,7 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
         *reinterpret_cast<f32x4*>(&sm.red[wave][l * C::TSZ + C::tslot(4 * q, col)]) = acc[l];
     }
     __syncthreads();
-    const float2 adam_sc = adam ? sm.adam_tab[it % kSLAdamTab] : make_float2(0.f, 1.f);
+    const float2 adam_sc = adam ? sm.adam_tab[it % kSplitAdamTab] : make_float2(0.f, 1.f);
     float g[NPT];
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
@@ -575,7 +575,7 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
     }
     if (plain_ok && it == 0) {  // the readers' hello granules (sent in their prologues)
       auto hello = [&](const void* buf) -> bool {
-        const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(xgmi_rsrc(buf), hidx * 16, 0, 16);
+        const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(xgmi_rsrc(buf), hidx * 16, 0, kDevCoherent);
         return (x.x ^ xgmi_hash3(x.y, x.z, x.w)) == htag && x.y == xcc;
       };
       if constexpr (!LAST) plain_next = next_local && hello(a.grad_in);
@@ -590,29 +590,18 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
     }
     // ---------------- optimizer (registers) + weight refresh (LDS)
     const float gs = a.hp.grad_scale;
-    if (adam) {
-      AdamScalars as = adam_consts(a.hp);
-      as.step_size = adam_sc.x;
-      as.bc2_sqrt = adam_sc.y;
-#pragma unroll
-      for (int k = 0; k < NPT; ++k) adam_update(pw[k], mr[k], vr[k], g[k] * gs, as);
-    } else {
-      const float lr = a.hp.lr_tab ? sm.adam_tab[it % kSLAdamTab].x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
-#pragma unroll
-      for (int k = 0; k < NPT; ++k) sgd_update(pw[k], mr[k], g[k] * gs, lr, mom, wd, t == 0);
-    }
+    split_optim_step<false, false>(a.hp, adam, adam_sc, sm.adam_tab, it, t == 0, gs, pf, pw, mr, vr, g);
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
       const float wv = S::rnd(pw[k]);
       sm.wb[pf[k]] = wv;
       sm.wb[pb[k]] = wv;
     }
-    (void)sink;
     if constexpr (LAST) {
       if (tid == 0 && lead && a.loss_log) a.loss_log[t % a.loss_log_cap] = use_dp ? gloss * gs : gloss;
     }
     __syncthreads();  // new weights visible; parked tiles consumed before the next park
-    if (tab && (it + 1) % kSLAdamTab == 0 && it + 1 < a.n_steps) {
+    if (tab && (it + 1) % kSplitAdamTab == 0 && it + 1 < a.n_steps) {
       fill_adam(it + 1);
       __syncthreads();
     }
@@ -631,22 +620,6 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
   }
   if (tid == 0) a.step[0] = t0 + a.n_steps;
 }
-
-// (IN, H, NL, OUT, FINAL_ACT, FIRST) of the split-batch stages: every DTP_SPLIT_SHAPES
-// stage (split_train.hip) -- the toy model's contiguous layer ranges
-#define DTP_SPLIT_LANES_SHAPES(X) \
-  X(2, 10, 5, 1, false, 1)        \
-  X(2, 10, 1, 10, true, 1)        \
-  X(2, 10, 2, 10, true, 1)        \
-  X(2, 10, 3, 10, true, 1)        \
-  X(2, 10, 4, 10, true, 1)        \
-  X(10, 10, 1, 10, true, 0)       \
-  X(10, 10, 2, 10, true, 0)       \
-  X(10, 10, 3, 10, true, 0)       \
-  X(10, 10, 1, 1, false, 0)       \
-  X(10, 10, 2, 1, false, 0)       \
-  X(10, 10, 3, 1, false, 0)       \
-  X(10, 10, 4, 1, false, 0)
 
 // every local stage's M members in one launch (co-resident by construction: 8 x n x M
 // blocks, the members at blocks 8 (s M + k)); shape ids are those of dtp_split_shape_id
@@ -667,26 +640,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     if (shape == id) split_lanes_body<Stage<I, H, N, O, F>, (bool)FI, !F>(a, smem, M, gk); \
   }                                                                                        \
   ++id;
-  DTP_SPLIT_LANES_SHAPES(X)
+  DTP_SPLIT_SHAPES(X)
 #undef X
 }
 
 }  // namespace dtp
 
 extern "C" {
-
-// the shape list must stay split_train.hip's DTP_SPLIT_SHAPES (shape ids are shared)
-int dtp_split_lanes_supported(int in, int h, int nl, int out, int final_act, int first) {
-  const int id = dtp_split_shape_id(in, h, nl, out, final_act, first);
-  if (id < 0) return 0;
-  int k = 0;
-#define X(I, H, N, O, F, FI)                                                                         \
-  if (k == id) return (in == I && h == H && nl == N && out == O && (bool)final_act == F && (bool)first == (bool)FI); \
-  ++k;
-  DTP_SPLIT_LANES_SHAPES(X)
-#undef X
-  return 0;
-}
 
 // bytes of a stage's member exchange buffer (grp_core.h: [2 parities][members][slot16])
 long long dtp_split_lanes_grp_bytes(int P, int members) {
@@ -699,63 +659,28 @@ int dtp_split_lanes_launch(const DtpSplitLaunch* L, void* stream) {
   if (!L || L->n < 1 || L->n > DTP_SPLIT_MAX_LOCAL) return set_err(-1, "split lanes: 1..8 stages per GPU");
   const int M = L->members;
   if (M < 1 || M > dtp::kSLMaxM) return set_err(-1, "split lanes: 1..8 members per stage");
-  static const int layers_of[] = {
-#define X(I, H, N, O, F, FI) N,
-      DTP_SPLIT_LANES_SHAPES(X)
-#undef X
-  };
-  static const int in_of[] = {
-#define X(I, H, N, O, F, FI) I,
-      DTP_SPLIT_LANES_SHAPES(X)
-#undef X
-  };
-  static const int out_of[] = {
-#define X(I, H, N, O, F, FI) O,
-      DTP_SPLIT_LANES_SHAPES(X)
-#undef X
-  };
-  static const int first_of[] = {
-#define X(I, H, N, O, F, FI) FI,
-      DTP_SPLIT_LANES_SHAPES(X)
-#undef X
-  };
-  static const int last_of[] = {
-#define X(I, H, N, O, F, FI) !F,
-      DTP_SPLIT_LANES_SHAPES(X)
-#undef X
-  };
-  constexpr int nshapes = sizeof(layers_of) / sizeof(layers_of[0]);
   int maxnl = 0;
   for (int i = 0; i < L->n; ++i) {
     const DtpSplitStageArgs& a = L->stage[i];
     const int id = L->shape_id[i];
-    if (id < 0 || id >= nshapes) return set_err(-2, "split lanes: stage shape not instantiated");
-    if (!a.params || !a.opt_m || !a.step || !a.status) return set_err(-1, "split lanes: missing buffers");
-    if (a.n_steps <= 0 || a.n_steps != L->stage[0].n_steps) return set_err(-1, "split lanes: n_steps");
-    if (a.optim != DTP_MODE_ADAM && a.optim != DTP_MODE_SGD) return set_err(-1, "split lanes: adam or sgd");
-    if (a.optim == DTP_MODE_ADAM && !a.opt_v) return set_err(-1, "split lanes: Adam needs opt_v");
+    if (id < 0 || id >= dtp::kSplitNumShapes) return set_err(-2, "split lanes: stage shape not instantiated");
+    const dtp::SplitShape& sh = dtp::kSplitShapes[id];
+    if (int rc = dtp::split_check_stage(a, sh, "split lanes", M)) return rc;
+    if (a.n_steps != L->stage[0].n_steps) return set_err(-1, "split lanes: n_steps");
     const dtp::SamplerCfg& s = a.smp;
     if (s.batch <= 0 || (s.batch + M - 1) / M > 64) return set_err(-1, "split lanes: batch / members must be <= 64");
     // the link buffers hold batch x 5 granules (dtp_split_link_bytes, width 10): batch x 4
     // lane slices, then the members' hello granules
     if (M > s.batch) return set_err(-1, "split lanes: at most one member per sample");
-    const bool first = first_of[id], last = last_of[id];
+    const bool first = sh.first, last = sh.last();
     if ((first || last) && (s.mode != dtp::SAMPLER_TABLE || !s.perm || s.perm_epochs <= 0 ||
                             (s.perm_epochs & (s.perm_epochs - 1))))
       return set_err(-1, "split lanes: the gathering stages read the device permutation ring (SAMPLER_TABLE)");
-    if (s.n * ((first ? in_of[id] : 0) + (last ? out_of[id] : 0)) > dtp::kSLData)
+    if (s.n * ((first ? sh.in : 0) + (last ? sh.out : 0)) > dtp::kSLData)
       return set_err(-1, "split lanes: dataset exceeds the LDS cache");
-    if (first && !a.X) return set_err(-1, "split lanes: the first stage needs the inputs");
-    if (last && !a.Y) return set_err(-1, "split lanes: the last stage needs the targets");
-    if (!first && (!a.act_in || !a.grad_out)) return set_err(-1, "split lanes: missing links to the previous stage");
-    if (!last && (!a.act_out || !a.grad_in)) return set_err(-1, "split lanes: missing links to the next stage");
-    if (a.dp_world > 1) {
-      if (!a.dp_peers || a.dp_world * M > dtp::kXgmiMaxWorld || a.dp_rank < 0 || a.dp_rank >= a.dp_world)
-        return set_err(-1, "split lanes: the cross-rank exchange serves ranks x members <= 8 with a peer table");
-    } else if (M > 1 && !a.grp_buf) {
+    if (a.dp_world <= 1 && M > 1 && !a.grp_buf)
       return set_err(-1, "split lanes: members > 1 need the member exchange buffer");
-    }
-    maxnl = layers_of[id] > maxnl ? layers_of[id] : maxnl;
+    maxnl = sh.nl > maxnl ? sh.nl : maxnl;
   }
   const dim3 grid(8 * L->n * M);
   if (maxnl <= 3) hipLaunchKernelGGL(dtp::split_lanes_kernel<3>, grid, dim3(256), 0, (hipStream_t)stream, *L);

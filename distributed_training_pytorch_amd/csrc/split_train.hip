@@ -27,16 +27,13 @@
 #include "mlp_core.h"
 #include "mlp_pipe.h"
 #include "optim_core.h"
+#include "split_core.h"
+#include "split_shapes.h"
 #include "xgmi_core.h"
 
 namespace dtp {
 
 constexpr int kSplitCache = 8192;  // floats of dataset staged in LDS (first / last stage)
-
-// cache policy of a link: sc1 = device scope (both stages on one GPU: the granules meet in
-// the device's last-level cache, no round trip to HBM), sc0 | sc1 = system scope
-// (neighbour on another GPU, uncached fine-grained buffer written over xGMI)
-constexpr int kDevCoherent = 16;
 
 // one lane's message: N floats as ceil(N/2) granules at granule index slot * G
 template <int N>
@@ -95,10 +92,6 @@ DTP_DEV void link_recv(const void* buf, int slot, unsigned ep, float (&v)[16], b
     __builtin_amdgcn_s_sleep(1);
   }
 }
-
-// Adam bias-correction scalars of the next kSplitAdamTab steps, formed once per that
-// many steps in f64 (torch's host math) -- not per step
-constexpr int kSplitAdamTab = 1024;
 
 template <class S>
 struct SplitSmem {
@@ -171,7 +164,7 @@ DTP_DEV void split_stage_body_v1(const DtpSplitStageArgs& a, unsigned char* smem
   const int t0 = a.step[0];
   // sampler cursor (epoch, batch of the epoch), advanced incrementally: no 64-bit
   // division per step
-  int epoch = t0 / smp.steps_per_epoch;
+  const int epoch = t0 / smp.steps_per_epoch;
   int bi = t0 - epoch * smp.steps_per_epoch;
   // the dataset index of this lane's sample at cursor (ep, b) -- requested a step ahead
   // (the ring / Feistel lookup overlaps the previous step's reduction and optimizer)
@@ -254,10 +247,7 @@ DTP_DEV void split_stage_body_v1(const DtpSplitStageArgs& a, unsigned char* smem
     const unsigned ep = (unsigned)t + 1u;
     const int bsz = min(smp.batch, smp.num_samples - bi * smp.batch);
     const bool valid = tid < bsz;
-    if (++bi == smp.steps_per_epoch) {
-      bi = 0;
-      ++epoch;
-    }
+    if (++bi == smp.steps_per_epoch) bi = 0;
     // ---- forward
     float h[NL + 1][16];
     if constexpr (FIRST) {
@@ -326,20 +316,7 @@ DTP_DEV void split_stage_body_v1(const DtpSplitStageArgs& a, unsigned char* smem
 
     // ---- optimizer (registers) + weight refresh (LDS)
     const float gs = a.hp.grad_scale;
-    if (adam) {
-      AdamScalars as = adam_consts(a.hp);
-      const float2 sc = sm.adam_tab[it % kSplitAdamTab];
-      as.step_size = sc.x;
-      as.bc2_sqrt = sc.y;
-#pragma unroll
-      for (int k = 0; k < NPT; ++k)
-        if (lp[k] >= 0) adam_update(pw[k], mr[k], vr[k], g[k] * gs, as);
-    } else {
-      const float lr = a.hp.lr_tab ? sm.adam_tab[it % kSplitAdamTab].x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
-#pragma unroll
-      for (int k = 0; k < NPT; ++k)
-        if (lp[k] >= 0) sgd_update(pw[k], mr[k], g[k] * gs, lr, mom, wd, t == 0);
-    }
+    split_optim_step<true, true>(a.hp, adam, float2{}, sm.adam_tab, it, t == 0, gs, lp, pw, mr, vr, g);
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
       if (lp[k] >= 0) sm.w[lp[k]] = pw[k];
@@ -440,7 +417,7 @@ DTP_DEV void split_stage_body_pipe(const DtpSplitStageArgs& a, unsigned char* sm
   if constexpr (LAST)
     for (int e = tid; e < smp.n * S::OUT; e += kBlock) sm.data[smp.n * XW + e] = a.Y[e];
   const int t0 = a.step[0];
-  int epoch = t0 / smp.steps_per_epoch;
+  const int epoch = t0 / smp.steps_per_epoch;
   int bi = t0 - epoch * smp.steps_per_epoch;
   auto index_at = [&](int ep, int b) -> int {
     if constexpr (!(FIRST || LAST)) {
@@ -527,10 +504,7 @@ DTP_DEV void split_stage_body_pipe(const DtpSplitStageArgs& a, unsigned char* sm
     const unsigned ep = (unsigned)t + 1u;
     const int bsz = min(smp.batch, smp.num_samples - bi * smp.batch);
     const bool valid = tid < bsz;
-    if (++bi == smp.steps_per_epoch) {
-      bi = 0;
-      ++epoch;
-    }
+    if (++bi == smp.steps_per_epoch) bi = 0;
     const float inv = 1.f / (float)(bsz * S::OUT);
     // ---- forward (the first block is read here; the others stream in layer by layer)
     float h[NL + 1][16];
@@ -659,18 +633,7 @@ DTP_DEV void split_stage_body_pipe(const DtpSplitStageArgs& a, unsigned char* sm
     SPLIT_STAMP(7);
     // ---- optimizer (registers) + weight refresh (LDS)
     const float gs = a.hp.grad_scale;
-    if (adam) {
-      AdamScalars as = adam_consts(a.hp);
-      const float2 sc = sm.adam_tab[it % kSplitAdamTab];
-      as.step_size = sc.x;
-      as.bc2_sqrt = sc.y;
-#pragma unroll
-      for (int k = 0; k < NPT; ++k) adam_update(pw[k], mr[k], vr[k], g[k] * gs, as);
-    } else {
-      const float lr = a.hp.lr_tab ? sm.adam_tab[it % kSplitAdamTab].x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
-#pragma unroll
-      for (int k = 0; k < NPT; ++k) sgd_update(pw[k], mr[k], g[k] * gs, lr, mom, wd, t == 0);
-    }
+    split_optim_step<true, false>(a.hp, adam, float2{}, sm.adam_tab, it, t == 0, gs, pfl, pw, mr, vr, g);
     scatter();
     if constexpr (LAST) {
       const int owner = use_dp ? xgmi_loss_tid<NPT>(P, kBlock) : 0;
@@ -713,25 +676,6 @@ DTP_DEV void split_stage_body(const DtpSplitStageArgs& a, unsigned char* smem) {
   split_stage_body_v1<S, FIRST, LAST>(a, smem);
 }
 
-// (IN, H, NL, OUT, FINAL_ACT, FIRST): the contiguous layer ranges of the toy model
-// as pipeline stages (the first entry: the whole model as ONE stage -- the split code's
-// baseline with no links, scripts/split_cost.py) (first stages read the 2-feature input; stages that end inside
-// the network carry the LeakyReLU of their last layer and are not last); the shape
-// id of a stage is its position in this list
-#define DTP_SPLIT_SHAPES(X)   \
-  X(2, 10, 5, 1, false, 1)    \
-  X(2, 10, 1, 10, true, 1)    \
-  X(2, 10, 2, 10, true, 1)    \
-  X(2, 10, 3, 10, true, 1)    \
-  X(2, 10, 4, 10, true, 1)    \
-  X(10, 10, 1, 10, true, 0)   \
-  X(10, 10, 2, 10, true, 0)   \
-  X(10, 10, 3, 10, true, 0)   \
-  X(10, 10, 1, 1, false, 0)   \
-  X(10, 10, 2, 1, false, 0)   \
-  X(10, 10, 3, 1, false, 0)   \
-  X(10, 10, 4, 1, false, 0)
-
 // every stage placed on one GPU, one workgroup each (blockIdx.x = local stage).  One
 // kernel holds the bodies of every stage shape of at most MAXNL layers: its registers are
 // allocated for the largest of them, so the 4- and 5-layer bodies (which need all 512
@@ -761,15 +705,13 @@ extern "C" {
 
 long long dtp_split_link_bytes(int width, int batch) { return (long long)batch * ((width + 1) / 2) * 16ll; }
 
-// shape id of a stage (its position in DTP_SPLIT_SHAPES), -1 if not instantiated
+// shape id of a stage (its position in DTP_SPLIT_SHAPES, split_shapes.h), -1 if not instantiated
 int dtp_split_shape_id(int in, int h, int nl, int out, int final_act, int first) {
-  int id = 0;
-#define X(I, H, N, O, F, FI)                                                                        \
-  if (in == I && h == H && nl == N && out == O && (bool)final_act == F && (bool)first == (bool)FI) \
-    return id;                                                                                      \
-  ++id;
-  DTP_SPLIT_SHAPES(X)
-#undef X
+  for (int id = 0; id < dtp::kSplitNumShapes; ++id) {
+    const dtp::SplitShape& s = dtp::kSplitShapes[id];
+    if (in == s.in && h == s.h && nl == s.nl && out == s.out && (bool)final_act == s.final_act && (bool)first == s.first)
+      return id;
+  }
   return -1;
 }
 
@@ -777,52 +719,21 @@ int dtp_split_stage_supported(int in, int h, int nl, int out, int final_act, int
   return dtp_split_shape_id(in, h, nl, out, final_act, first) >= 0;
 }
 
-static int validate_stage(const DtpSplitStageArgs* a, int first, int last) {
-  using dtp::set_err;
-  if (!a || !a->params || !a->opt_m || !a->step || !a->status) return set_err(-1, "split stage: missing buffers");
-  if (a->n_steps <= 0) return set_err(-1, "split stage: n_steps must be positive");
-  if (a->smp.batch <= 0 || a->smp.batch > dtp::kBlock || a->smp.mode == dtp::SAMPLER_EXPLICIT)
-    return set_err(-1, "split stage: batch must be 1..256 samples (one lane each) with a device sampler");
-  if (a->optim != DTP_MODE_ADAM && a->optim != DTP_MODE_SGD) return set_err(-1, "split stage: adam or sgd");
-  if (a->optim == DTP_MODE_ADAM && !a->opt_v) return set_err(-1, "split stage: Adam needs opt_v");
-  if (first && !a->X) return set_err(-1, "split stage: the first stage needs the inputs");
-  if (last && !a->Y) return set_err(-1, "split stage: the last stage needs the targets");
-  if (!first && (!a->act_in || !a->grad_out)) return set_err(-1, "split stage: missing links to the previous stage");
-  if (!last && (!a->act_out || !a->grad_in)) return set_err(-1, "split stage: missing links to the next stage");
-  if (last && a->loss_log && a->loss_log_cap <= 0) return set_err(-1, "split stage: loss_log_cap");
-  if (a->dp_world > 1 && (!a->dp_peers || a->dp_world > dtp::kXgmiMaxWorld || a->dp_rank < 0 ||
-                          a->dp_rank >= a->dp_world))
-    return set_err(-1, "split stage: data-parallel exchange serves 1..8 ranks with a peer table");
-  return 0;
-}
-
 // the stages of one GPU as ONE launch (co-resident workgroups)
 int dtp_split_launch(const DtpSplitLaunch* L, void* stream) {
   using dtp::set_err;
   if (!L || L->n < 1 || L->n > DTP_SPLIT_MAX_LOCAL) return set_err(-1, "split launch: 1..8 stages per GPU");
-  static const int first_of[] = {
-#define X(I, H, N, O, F, FI) FI,
-      DTP_SPLIT_SHAPES(X)
-#undef X
-  };
-  static const int last_of[] = {
-#define X(I, H, N, O, F, FI) !F,
-      DTP_SPLIT_SHAPES(X)
-#undef X
-  };
-  static const int layers_of[] = {
-#define X(I, H, N, O, F, FI) N,
-      DTP_SPLIT_SHAPES(X)
-#undef X
-  };
   int maxnl = 0;
-  constexpr int nshapes = sizeof(first_of) / sizeof(first_of[0]);
   for (int i = 0; i < L->n; ++i) {
+    const DtpSplitStageArgs& a = L->stage[i];
     const int id = L->shape_id[i];
-    if (id < 0 || id >= nshapes) return set_err(-2, "split launch: stage shape not instantiated");
-    if (int rc = validate_stage(&L->stage[i], first_of[id], last_of[id])) return rc;
-    if (L->stage[i].n_steps != L->stage[0].n_steps) return set_err(-1, "split launch: stages disagree on n_steps");
-    maxnl = layers_of[id] > maxnl ? layers_of[id] : maxnl;
+    if (id < 0 || id >= dtp::kSplitNumShapes) return set_err(-2, "split launch: stage shape not instantiated");
+    const dtp::SplitShape& sh = dtp::kSplitShapes[id];
+    if (int rc = dtp::split_check_stage(a, sh, "split stage", 1)) return rc;
+    if (a.smp.batch <= 0 || a.smp.batch > dtp::kBlock || a.smp.mode == dtp::SAMPLER_EXPLICIT)
+      return set_err(-1, "split stage: batch must be 1..256 samples (one lane each) with a device sampler");
+    if (a.n_steps != L->stage[0].n_steps) return set_err(-1, "split launch: stages disagree on n_steps");
+    maxnl = sh.nl > maxnl ? sh.nl : maxnl;
   }
   if (maxnl <= 3) hipLaunchKernelGGL(dtp::split_multi_kernel<3>, dim3(L->n), dim3(dtp::kBlock), 0, (hipStream_t)stream, *L);
   else hipLaunchKernelGGL(dtp::split_multi_kernel<5>, dim3(L->n), dim3(dtp::kBlock), 0, (hipStream_t)stream, *L);

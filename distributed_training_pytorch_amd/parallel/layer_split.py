@@ -516,7 +516,7 @@ class FusedLayerSplit:
         from ..data.sampler import SAMPLER_DIST_SHUFFLE
 
         K = len(self.stage_specs)
-        ok = all(lib.dtp_split_lanes_supported(ss.in_features, ss.hidden, ss.n_layers, ss.out_features,
+        ok = all(lib.dtp_split_stage_supported(ss.in_features, ss.hidden, ss.n_layers, ss.out_features,
                                                int(ss.final_act), int(s == 0))
                  for s, ss in enumerate(self.stage_specs))
         ok = ok and geom.mode == SAMPLER_DIST_SHUFFLE

@@ -49,8 +49,9 @@ to each other).  A cell takes the margin only where its excess comes from ``Y`` 
 unusually small draw, shown from the reference's own numbers in
 ``profiles/split_matrix/README.md``; the margin is a function of the reference only.
 
-**Instances.**  :data:`INSTANCES` is written out from ``DTP_SPLIT_SHAPES`` and
-``DTP_SPLIT_LANES_SHAPES`` (the same twelve stage shapes, ids shared).  ``split_stage_body()``
+**Instances.**  :data:`INSTANCES` is written out from ``DTP_SPLIT_SHAPES`` of
+``csrc/split_shapes.h`` (twelve stage shapes; both engines expand the one list, so the ids are
+shared).  ``split_stage_body()``
 runs a one-layer stage on ``split_stage_body_v1`` and a stage of >= 2 layers on
 ``split_stage_body_pipe`` while its dataset slice ``n (XW + YW)`` fits ``kSplitCache`` = 8192
 floats, else on v1 (:func:`stage_body`).  A middle stage gathers nothing (0 <= 8192), so the
@@ -77,7 +78,7 @@ K_SL_MAX_M = 8         # kSLMaxM
 TIMEOUT_US = 500_000   # a dead link ends as the engine's RuntimeError within half a second
 NL = TOY_SPEC.n_layers
 
-# (IN, H, NL, OUT, FINAL_ACT, FIRST): DTP_SPLIT_SHAPES / DTP_SPLIT_LANES_SHAPES, id = position
+# (IN, H, NL, OUT, FINAL_ACT, FIRST): DTP_SPLIT_SHAPES (csrc/split_shapes.h), id = position
 SHAPES = [
     (2, 10, 5, 1, False, 1),
     (2, 10, 1, 10, True, 1), (2, 10, 2, 10, True, 1), (2, 10, 3, 10, True, 1), (2, 10, 4, 10, True, 1),
@@ -88,7 +89,7 @@ SHAPES = [
 
 def _instances():
     """(engine, body, shape id) of every stage instance a default build can run -- written out
-    from the two X-macro lists, NOT derived from the cells."""
+    from the X-macro list, NOT derived from the cells."""
     out = [("lanes", "lanes", i) for i in range(12)]                 # split_lanes_kernel: one body per shape
     out += [("one", "pipe", i) for i in (0, 2, 3, 4, 6, 7, 9, 10, 11)]  # >= 2 layers, dataset slice cached
     out += [("one", "v1", i) for i in (1, 5, 8)]                      # the one-layer shapes

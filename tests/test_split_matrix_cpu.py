@@ -63,19 +63,25 @@ def test_every_split_instance_has_a_cell():
 
 
 def test_split_shape_table_is_the_x_macro_list():
-    """SHAPES against the two lists in the sources, and the partitions against the shapes."""
+    """SHAPES against the one list in ``csrc/split_shapes.h``, which both engines' sources expand
+    and neither redefines, and the partitions against the shapes."""
     import os
     import re
 
     root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "distributed_training_pytorch_amd",
                         "csrc")
-    for name, macro in (("split_train.hip", "DTP_SPLIT_SHAPES"), ("split_lanes.hip", "DTP_SPLIT_LANES_SHAPES")):
+    src = open(os.path.join(root, "split_shapes.h")).read()
+    assert src.count("#define DTP_SPLIT_SHAPES(X)") == 1
+    body = src[src.index("#define DTP_SPLIT_SHAPES(X)"):]
+    body = body[:body.index("\n\n")]
+    rows = [(int(a), int(b), int(c), int(d), e == "true", int(f))
+            for a, b, c, d, e, f in re.findall(r"X\((\d+), (\d+), (\d+), (\d+), (true|false), (\d)\)", body)]
+    assert rows == sp.SHAPES
+    for name in ("split_train.hip", "split_lanes.hip"):
         src = open(os.path.join(root, name)).read()
-        body = src[src.index(f"#define {macro}(X)"):]
-        body = body[:body.index("\n\n")]
-        rows = [(int(a), int(b), int(c), int(d), e == "true", int(f))
-                for a, b, c, d, e, f in re.findall(r"X\((\d+), (\d+), (\d+), (\d+), (true|false), (\d)\)", body)]
-        assert rows == sp.SHAPES, name
+        assert not re.search(r"#\s*define\s+DTP_SPLIT\w*SHAPES", src), name  # no list of its own
+        assert not re.search(r"X\(\d+, \d+, \d+, \d+, (true|false), \d\)", src), name
+        assert '#include "split_shapes.h"' in src and re.search(r"^\s*DTP_SPLIT_SHAPES\(X\)$", src, re.M), name
     parts = sp.all_partitions()
     assert len(parts) == len(set(parts)) == 16
     for p in parts:
