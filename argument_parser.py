@@ -27,9 +27,12 @@ def build_parser(description: str | None = None) -> argparse.ArgumentParser:
     p.add_argument("--iters", type=int, default=1000, help="training iterations (demo.py:88)")
     p.add_argument("--batch_size", type=int, default=256, help="per-rank batch (demo.py:145)")
     p.add_argument("--lr", type=float, default=1e-3)
-    p.add_argument("--optimizer", choices=["adam", "sgd"], default="adam")
+    p.add_argument("--optimizer", choices=["adam", "sgd", "adamw"], default="adam",
+                   help="adamw = torch.optim.AdamW: the decay is decoupled (p *= 1 - lr_t x --weight_decay ahead of "
+                        "Adam's update, inside the same kernels); adam / sgd add --weight_decay x p to the gradient")
     p.add_argument("--momentum", type=float, default=0.0)
-    p.add_argument("--weight_decay", type=float, default=0.0)
+    p.add_argument("--weight_decay", type=float, default=0.0,
+                   help="default 0 for every optimizer (torch.optim.AdamW's own default is 0.01: pass it to match)")
     p.add_argument("--accumulate_grad_batches", type=int, default=1,
                    help="A > 1: one optimizer step consumes A consecutive batches (the gradient is the mean of their "
                         "mean-loss gradients; clipping, weight decay, the schedule and Adam's bias correction act "

@@ -162,7 +162,7 @@ def main(argv=None):
     if pbar is not None:
         pbar.close()
     logger.finish()
-    summary.update({"stages": len(devs), "microbatches": config.microbatches})
+    summary.update({"stages": len(devs), "microbatches": config.microbatches, "optimizer": ocfg.label})
     summary.update(runner._lr_summary(config, int(summary.get("iters", config.iters))))
     rank_print(rank, "Finished")
     if rank == 0:

@@ -62,7 +62,7 @@ class Hyper(ctypes.Structure):
         ("grad_scale", c_float),
         ("lr_tab", c_void_p),     # float64 [lr_tab_len] on the device (ops.schedule), or null: lr
         ("lr_tab_len", c_int),
-        ("pad_", c_int),
+        ("decoupled_wd", c_int),  # 1: AdamW (p *= 1 - lr_t * weight_decay ahead of Adam's update); Adam only
     ]
 
 

@@ -23,8 +23,11 @@ def plain_toy_model(slope: float = 0.01) -> nn.Module:
 
 class StockLoop:
     def __init__(self, dataset, device, batch: int = 256, seed: int = 0, ddp: bool = True,
-                 clip_grad_norm: float = 0.0, clip_grad_value: float = 0.0, schedule=None, accumulate: int = 1):
-        """``schedule``: an ``ops.schedule.LrSchedule``; both Adams then follow its values
+                 clip_grad_norm: float = 0.0, clip_grad_value: float = 0.0, schedule=None, accumulate: int = 1,
+                 optim=None):
+        """``optim``: an ``ops.optim.OptimConfig`` whose ``torch_optimizer`` both models then use
+        (``--optimizer adamw``); None: the reference's verbatim ``Adam(lr=1e-3)`` pair.
+        ``schedule``: an ``ops.schedule.LrSchedule``; both Adams then follow its values
         through ``torch.optim.lr_scheduler.LambdaLR`` (stepped after every optimizer step).
         ``accumulate``: batches per optimizer step, the torch idiom (``loss / A``, ``no_sync`` on
         DDP for the first ``A - 1`` backwards, the step on the last)."""
@@ -43,8 +46,12 @@ class StockLoop:
             ids = [device.index] if device.type == "cuda" else None
             self.mx = DDP(self.mx, device_ids=ids)
             self.my = DDP(self.my, device_ids=ids)
-        self.ox = torch.optim.Adam(self.mx.parameters(), lr=1e-3)
-        self.oy = torch.optim.Adam(self.my.parameters(), lr=1e-3)
+        if optim is None:
+            self.ox = torch.optim.Adam(self.mx.parameters(), lr=1e-3)
+            self.oy = torch.optim.Adam(self.my.parameters(), lr=1e-3)
+        else:
+            self.ox = optim.torch_optimizer(self.mx.parameters())
+            self.oy = optim.torch_optimizer(self.my.parameters())
         self.schedulers = []
         if schedule is not None:
             # base lr 1.0 x the table's value: the param group's lr is the value itself

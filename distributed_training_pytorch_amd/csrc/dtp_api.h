@@ -27,7 +27,12 @@ struct DtpHyper {
   // captured graphs can run.
   const double* lr_tab;
   int lr_tab_len;
-  int pad_;
+  // 1: AdamW, torch.optim.Adam(decoupled_weight_decay=True): the step after t taken steps first
+  // scales p by d_t = (float)(1.0 - lr_t * weight_decay) (f64 product and difference, one fp32
+  // multiply), then runs Adam's update on the gradient as it arrived -- weight_decay enters
+  // neither g nor m / v.  Adam modes only; 0: weight_decay * p is added to the gradient.
+  // (It takes the place of a padding int: the block's size and every offset are unchanged.)
+  int decoupled_wd;
 };
 
 struct DtpTrainArgs {

@@ -3,6 +3,7 @@
 // (mlp_core.h).  Equivalent of one MultiGPUModel stage of
 // demo_one_model_multi_gpu.py:17-42 and of nn.Sequential fwd/bwd in
 // toy_model_and_data.py:8-25.
+#include <type_traits>
 #include <string>
 
 #include "dtp_api.h"
@@ -68,7 +69,7 @@ DTP_DEV void stage_fwd_body(const DtpStageArgs& a, float* sw) {
 // autograd node and its optimizer step in ONE launch, ops/mlp.py "param-backward
 // fusion"): the thread that sums dW_p also updates p, m[p], v[p] -- the weights were
 // staged in LDS before, so no wave reads a global weight after it is updated.  The same
-// adam_update / sgd_update as flat_optimizer_kernel: bitwise the unfused pair.
+// adam_update (adamw_update_v) / sgd_update as flat_optimizer_kernel: bitwise the unfused pair.
 template <class S, bool WANT_DX, bool OPT>
 DTP_DEV void stage_bwd_body(const DtpStageArgs& a, const DtpOptArgs& o) {
   __shared__ __align__(16) struct {
@@ -122,17 +123,24 @@ DTP_DEV void stage_bwd_body(const DtpStageArgs& a, const DtpOptArgs& o) {
     const bool zg = o.flags & DTP_OPT_ZERO_GRAD;
     const float gs = o.hp.grad_scale;
     if (o.kind == DTP_MODE_ADAM) {
-      const AdamScalars sc = adam_scalars(o.hp, t + 1);
-      for (int p = tid; p < S::P; p += kBlock) {
-        const float g = sum_partial_tiles<S>(&sm.stage[0][0], tile_pos<S>(p), 4);
-        const float gt = a.accumulate ? a.grad_params[p] + g : g;
-        float w = o.params[p], mi = o.opt_m[p], vi = o.opt_v[p];
-        adam_update(w, mi, vi, gt * gs, sc);
-        o.params[p] = w;
-        o.opt_m[p] = mi;
-        o.opt_v[p] = vi;
-        a.grad_params[p] = zg ? 0.f : gt;
-      }
+      // two versions behind one block-uniform test, as flat_optimizer_kernel: DEC = false is the
+      // loop as it was before AdamW existed
+      const auto adam_rows = [&](auto DEC) {
+        constexpr bool kDec = decltype(DEC)::value;
+        const AdamScalars sc = adam_scalars_v<kDec>(o.hp, t + 1);
+        for (int p = tid; p < S::P; p += kBlock) {
+          const float g = sum_partial_tiles<S>(&sm.stage[0][0], tile_pos<S>(p), 4);
+          const float gt = a.accumulate ? a.grad_params[p] + g : g;
+          float w = o.params[p], mi = o.opt_m[p], vi = o.opt_v[p];
+          adamw_update_v<kDec>(w, mi, vi, gt * gs, sc);
+          o.params[p] = w;
+          o.opt_m[p] = mi;
+          o.opt_v[p] = vi;
+          a.grad_params[p] = zg ? 0.f : gt;
+        }
+      };
+      if (decoupled_on(o.hp)) adam_rows(std::true_type{});
+      else adam_rows(std::false_type{});
     } else {
       const float lr = (float)lr_of(o.hp, t), mom = (float)o.hp.momentum, wd = (float)o.hp.weight_decay;
       for (int p = tid; p < S::P; p += kBlock) {
@@ -244,6 +252,8 @@ extern "C" {
 int dtp_mlp_stage_bwd_opt(const DtpStageMulti* m, const DtpOptArgs* o, int in, int h, int nl, int out, int final_act,
                           void* stream) {
   if (!m || !o) return set_err(-1, "stage_bwd_opt: null arguments");
+  if (o->hp.decoupled_wd && o->kind != DTP_MODE_ADAM)
+    return set_err(-1, "stage_bwd_opt: decoupled weight decay (AdamW) is Adam's: SGD has no decoupled form");
   // the backward is still writing the gradient: its norm cannot be formed in the same launch
   if (o->max_norm != 0.f || o->clip_value != 0.f)
     return set_err(-6, "stage_bwd_opt: gradient clipping needs the backward launched before the optimizer step");

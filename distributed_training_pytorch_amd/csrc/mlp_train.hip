@@ -243,6 +243,8 @@ int validate_train(const DtpTrainArgs* a, int mode) {
   if (mode == DTP_MODE_GRAD && !a->grad_out) return set_err(-1, "MODE_GRAD needs grad_out");
   if (mode != DTP_MODE_GRAD && !a->opt_m) return set_err(-1, "optimizer modes need opt_m");
   if ((mode == DTP_MODE_ADAM || mode == DTP_MODE_XGMI_ADAM) && !a->opt_v) return set_err(-1, "Adam needs opt_v");
+  if (a->hp.decoupled_wd && dtp::mode_sgd(mode))
+    return set_err(-1, "decoupled weight decay (AdamW) is Adam's: SGD has no decoupled form");
   if (a->max_norm < 0.f || a->clip_value < 0.f || a->max_norm != a->max_norm || a->clip_value != a->clip_value)
     return set_err(-4, "clipping: max_norm and clip_value must not be negative");
   if (a->max_norm > 0.f && a->clip_value > 0.f) return set_err(-4, "clipping: max_norm and clip_value are exclusive");

@@ -700,6 +700,7 @@ void mlp_train_lanes_kernel(DtpTrainArgs a) {
       AdamScalars as = adam_consts(a.hp);
       as.step_size = adam_sc.x;
       as.bc2_sqrt = adam_sc.y;
+      if constexpr (kAdam) decoupled_decay_step(a.hp, as, t0 + it, pw);  // AdamW: p *= d_t
       const float lr = ltab ? adam_sc.x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
       if constexpr (kAccum) {
         // the twin clips behind a run-time branch (block-uniform: it comes from the argument

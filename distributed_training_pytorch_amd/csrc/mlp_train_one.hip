@@ -397,6 +397,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(1, 1))) 
       AdamScalars as = adam_consts(a.hp);
       as.step_size = adam_sc.x;
       as.bc2_sqrt = adam_sc.y;
+      if constexpr (kAdam) decoupled_decay_step(a.hp, as, t, pw);  // AdamW: p *= d_t
       const float lr = ltab ? adam_sc.x : (float)a.hp.lr, mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
       // branch-free over the thread's NPT slots (slots past P hold zeros and store
       // into sm.sink), so the compiler can interleave the slots' dependency chains

@@ -10,6 +10,7 @@
 // optimizer) is a second instance of the same kernel body: the row's norm is formed in
 // the optimizer's own launch (rows of one block) or from a norm launch's fp64 partials.
 #include "dtp_api.h"
+#include <type_traits>
 #include "optim_core.h"
 
 namespace dtp {
@@ -170,8 +171,13 @@ DTP_DEV void flat_optimizer_body(const DtpOptArgs& a) {
   const uintptr_t ph = (uintptr_t)p & 15;
   const bool vec = v && (((uintptr_t)m & 15) == ph) && (((uintptr_t)v & 15) == ph) && (((uintptr_t)g & 15) == ph) &&
                    (ph & 3) == 0 && (!sh || (ph == 0 && (a.P & 3) == 0 && ((uintptr_t)sh & 7) == 0));
-  if (a.kind == DTP_MODE_ADAM && vec) {
-    const AdamScalars s = adam_scalars(a.hp, t + 1);
+  // The Adam rows in two versions behind one block-uniform test: DEC = false is the loop as
+  // it was before AdamW existed (what a launch with weight_decay == 0 or the coupled decay
+  // runs), DEC = true scales each parameter by the step's d_t first (optim_core.h)
+  const auto adam_rows = [&](auto DEC) {
+  constexpr bool kDec = decltype(DEC)::value;
+  if (vec) {
+    const AdamScalars s = adam_scalars_v<kDec>(a.hp, t + 1);
     const int head = min((int)((16 - ph) & 15) >> 2, a.P);
     const int P4 = (a.P - head) >> 2, tail0 = head + 4 * P4;
     float4* p4 = reinterpret_cast<float4*>(p + head);
@@ -182,10 +188,10 @@ DTP_DEV void flat_optimizer_body(const DtpOptArgs& a) {
       float4 w = p4[i], mi = m4[i], vi = v4[i];
       const float4 gi = g4[i];
       if (zg) reinterpret_cast<float4*>(gz + head)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      adam_update(w.x, mi.x, vi.x, gx(gi.x), s);
-      adam_update(w.y, mi.y, vi.y, gx(gi.y), s);
-      adam_update(w.z, mi.z, vi.z, gx(gi.z), s);
-      adam_update(w.w, mi.w, vi.w, gx(gi.w), s);
+      adamw_update_v<kDec>(w.x, mi.x, vi.x, gx(gi.x), s);
+      adamw_update_v<kDec>(w.y, mi.y, vi.y, gx(gi.y), s);
+      adamw_update_v<kDec>(w.z, mi.z, vi.z, gx(gi.z), s);
+      adamw_update_v<kDec>(w.w, mi.w, vi.w, gx(gi.w), s);
       p4[i] = w;
       m4[i] = mi;
       v4[i] = vi;
@@ -198,18 +204,18 @@ DTP_DEV void flat_optimizer_body(const DtpOptArgs& a) {
       float w = p[idx], mi = m[idx], vi = v[idx];
       const float gv = g[idx];
       if (zg) gz[idx] = 0.f;
-      adam_update(w, mi, vi, gx(gv), s);
+      adamw_update_v<kDec>(w, mi, vi, gx(gv), s);
       p[idx] = w;
       m[idx] = mi;
       v[idx] = vi;
       if (sh) sh[idx] = (__bf16)w;
     }
-  } else if (a.kind == DTP_MODE_ADAM && sh) {
+  } else if (sh) {
     // unaligned rows (odd P: every bias-terminated MLP) with a shadow: two elements per
     // thread, so the shadow is written as one 4-byte bf16 pair per lane (the shadow's
     // rows are 512-byte aligned, ComputeShadow); single 2-byte stores per lane ran the
     // whole kernel 15 % slower
-    const AdamScalars s = adam_scalars(a.hp, t + 1);
+    const AdamScalars s = adam_scalars_v<kDec>(a.hp, t + 1);
     const int P2 = (a.P + 1) >> 1;
     for (int j = blockIdx.x * kBlock + threadIdx.x; j < P2; j += gridDim.x * kBlock) {
       const int i = 2 * j;
@@ -222,12 +228,12 @@ DTP_DEV void flat_optimizer_body(const DtpOptArgs& a) {
         gz[i] = 0.f;
         if (two) gz[i + 1] = 0.f;
       }
-      adam_update(w0, m0, v0, gx(g0), s);
+      adamw_update_v<kDec>(w0, m0, v0, gx(g0), s);
       p[i] = w0;
       m[i] = m0;
       v[i] = v0;
       if (two) {
-        adam_update(w1, m1, v1, gx(g1), s);
+        adamw_update_v<kDec>(w1, m1, v1, gx(g1), s);
         p[i + 1] = w1;
         m[i + 1] = m1;
         v[i + 1] = v1;
@@ -236,17 +242,22 @@ DTP_DEV void flat_optimizer_body(const DtpOptArgs& a) {
         sh[i] = (__bf16)w0;
       }
     }
-  } else if (a.kind == DTP_MODE_ADAM) {
-    const AdamScalars s = adam_scalars(a.hp, t + 1);
+  } else {
+    const AdamScalars s = adam_scalars_v<kDec>(a.hp, t + 1);
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.P; i += gridDim.x * kBlock) {
       float w = p[i], mi = m[i], vi = v[i];
       const float gv = g[i];
       if (zg) gz[i] = 0.f;
-      adam_update(w, mi, vi, gx(gv), s);
+      adamw_update_v<kDec>(w, mi, vi, gx(gv), s);
       p[i] = w;
       m[i] = mi;
       v[i] = vi;
     }
+  }
+  };
+  if (a.kind == DTP_MODE_ADAM) {
+    if (decoupled_on(a.hp)) adam_rows(std::true_type{});
+    else adam_rows(std::false_type{});
   } else {
     const float lr = (float)lr_of(a.hp, t), mom = (float)a.hp.momentum, wd = (float)a.hp.weight_decay;
     for (int i = blockIdx.x * kBlock + threadIdx.x; i < a.P; i += gridDim.x * kBlock) {
@@ -323,6 +334,8 @@ extern "C" int dtp_clip_grad_norm(float* grad, int n_models, int P, float max_no
 extern "C" int dtp_flat_optimizer(const DtpOptArgs* a, void* stream) {
   if (!a || a->P <= 0 || a->n_models <= 0) return -1;
   if (a->kind != DTP_MODE_ADAM && a->kind != DTP_MODE_SGD) return -2;
+  if (a->hp.decoupled_wd && a->kind != DTP_MODE_ADAM)
+    return set_err(-1, "flat_optimizer: decoupled weight decay (AdamW) is Adam's: SGD has no decoupled form");
   if (a->hp.lr_tab && a->hp.lr_tab_len <= 0) return set_err(-6, "flat_optimizer: a learning-rate table needs at least one entry");
   hipStream_t st = (hipStream_t)stream;
   // small models (the toy's 371 parameters): one block per model loops over its

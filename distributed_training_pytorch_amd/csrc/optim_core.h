@@ -3,6 +3,7 @@
 // reference: Adam(lr=1e-3), demo.py:80-81) element for element:
 //   Adam:  m.lerp_(g, 1-b1); v.mul_(b2).addcmul_(g, g, 1-b2);
 //          denom = sqrt(v)/sqrt(1-b2^t) + eps; p.addcdiv_(m, denom, -lr/(1-b1^t))
+//   AdamW (hp.decoupled_wd): p.mul_(1 - lr * wd) ahead of Adam's update, wd not in g
 //   SGD :  buf = g (first step) | buf*mom + g;  p.add_(buf, -lr)
 // with the scalar bias corrections formed in double, as torch does on the host.
 #pragma once
@@ -13,6 +14,11 @@ namespace dtp {
 
 struct AdamScalars {
   float step_size, bc2_sqrt, one_m_b1, b2, one_m_b2, eps, wd;
+  // AdamW (hp.decoupled_wd with a weight_decay != 0): decoupled = 1, wd = 0 -- the decay does not
+  // enter the gradient -- and decay = d_t = (float)(1.0 - lr_t * weight_decay), the factor of p
+  // ahead of the update.  Else decoupled = 0, decay = 1 and wd as it always was.
+  float decay;
+  int decoupled;
 };
 
 // the learning rate of the step taken after t steps (t = the step counter before the step,
@@ -22,17 +28,37 @@ DTP_DEV double lr_of(const DtpHyper& hp, long long t) {
   return hp.lr_tab[t < hp.lr_tab_len ? t : hp.lr_tab_len - 1];
 }
 
+// AdamW's factor of p for a step at rate lr: 1 - lr * weight_decay in f64 as torch forms it on the
+// host -- a product, then a difference, whatever -ffp-contract the including source builds with --
+// rounded to fp32 once.
+DTP_DEV float decoupled_decay(const DtpHyper& hp, double lr) {
+#pragma clang fp contract(off)
+  const double prod = lr * hp.weight_decay;
+  return (float)(1.0 - prod);
+}
+
+// is this launch AdamW's?  weight_decay == 0 with the flag is plain Adam, to the instruction
+DTP_DEV bool decoupled_on(const DtpHyper& hp) { return hp.decoupled_wd != 0 && hp.weight_decay != 0.0; }
+
+// wd / decay / decoupled of the scalars for a step at rate lr
+DTP_DEV void adam_decay_fields(AdamScalars& s, const DtpHyper& hp, double lr) {
+  s.decoupled = decoupled_on(hp) ? 1 : 0;
+  s.wd = s.decoupled ? 0.f : (float)hp.weight_decay;
+  s.decay = s.decoupled ? decoupled_decay(hp, lr) : 1.f;
+}
+
 DTP_DEV AdamScalars adam_scalars(const DtpHyper& hp, long long t1) {
   AdamScalars s;
   const double bc1 = 1.0 - pow_int(hp.beta1, (uint64_t)t1);
   const double bc2 = 1.0 - pow_int(hp.beta2, (uint64_t)t1);
-  s.step_size = (float)(lr_of(hp, t1 - 1) / bc1);
+  const double lr = lr_of(hp, t1 - 1);
+  s.step_size = (float)(lr / bc1);
   s.bc2_sqrt = (float)sqrt(bc2);
   s.one_m_b1 = (float)(1.0 - hp.beta1);
   s.b2 = (float)hp.beta2;
   s.one_m_b2 = (float)(1.0 - hp.beta2);
   s.eps = (float)hp.eps;
-  s.wd = (float)hp.weight_decay;
+  adam_decay_fields(s, hp, lr);
   return s;
 }
 
@@ -50,7 +76,8 @@ DTP_DEV AdamScalars adam_scalars_from_pow(const DtpHyper& hp, double b1t, double
   return s;
 }
 
-// the step-independent part of the scalars (step_size / bc2_sqrt filled by the caller)
+// the step-independent part of the scalars (step_size / bc2_sqrt filled by the caller; decay is
+// that of hp.lr: the kernels that use these decay through decoupled_decay_step below)
 DTP_DEV AdamScalars adam_consts(const DtpHyper& hp) {
   AdamScalars s;
   s.step_size = 0.f;
@@ -59,7 +86,7 @@ DTP_DEV AdamScalars adam_consts(const DtpHyper& hp) {
   s.b2 = (float)hp.beta2;
   s.one_m_b2 = (float)(1.0 - hp.beta2);
   s.eps = (float)hp.eps;
-  s.wd = (float)hp.weight_decay;
+  adam_decay_fields(s, hp, hp.lr);
   return s;
 }
 
@@ -97,6 +124,50 @@ DTP_DEV void adam_update(float& p, float& m, float& v, float g, const AdamScalar
   const float denom = sqrtf(v) / s.bc2_sqrt + s.eps;
   p = fmaf(-s.step_size, m / denom, p);            // p.addcdiv_(m, denom, -step_size)
 #endif
+}
+
+// The flat optimizer and the stage backward fused with it run their Adam loops in two versions
+// behind one block-uniform test (decoupled_on): DEC = false is the loop as it was before AdamW
+// existed -- wd as always, no decay factor alive -- so a launch with weight_decay == 0 or the
+// coupled decay executes what it did; DEC = true is AdamW: p *= d_t, then Adam's update on the
+// decayed p with the gradient as it arrived (wd = 0).  d_t is the step's own
+// (adam_scalars: lr_of by the device step counter) and block-uniform: kept in a scalar register.
+template <bool DEC>
+DTP_DEV AdamScalars adam_scalars_v(const DtpHyper& hp, long long t1) {
+  AdamScalars s = adam_scalars(hp, t1);
+  if constexpr (DEC) {
+    s.wd = 0.f;
+    s.decoupled = 1;
+    s.decay = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, s.decay)));
+  } else {
+    s.wd = (float)hp.weight_decay;
+    s.decoupled = 0;
+    s.decay = 1.f;
+  }
+  return s;
+}
+
+template <bool DEC>
+DTP_DEV void adamw_update_v(float& p, float& m, float& v, float g, const AdamScalars& s) {
+  if constexpr (DEC) p *= s.decay;
+  adam_update(p, m, v, g, s);
+}
+
+// AdamW in the kernels that keep a thread's parameters in registers over the steps of a launch
+// (the fused step, the layer-split stages): the decay of the step taken after t steps on all of
+// a thread's slots, ahead of the unrolled adam_update calls, behind ONE block-uniform branch per
+// step and with no state carried from step to step -- nested inside adam_update, with the rate
+// requested early in the step behind a branch of its own, it cost the default launch 0.085 us
+// of its 2.59 us step (profiles/adamw).  The rate comes from lr_of (a per-step row
+// {lr_t / (1 - b1^t), ...} does not give lr_t back): under a schedule one read of the device
+// table, on the decoupled path only; without one, hp.lr.
+template <int N>
+DTP_DEV void decoupled_decay_step(const DtpHyper& hp, const AdamScalars& s, long long t, float (&p)[N]) {
+  if (s.decoupled) {
+    const float d = decoupled_decay(hp, lr_of(hp, t));
+#pragma unroll
+    for (int k = 0; k < N; ++k) p[k] *= d;
+  }
 }
 
 // torch.nn.utils.clip_grad_norm_'s coefficient from the fp32 total norm, operation for

@@ -26,10 +26,10 @@ constexpr int kSplitAdamTab = 1024;
 // ROW_LATE: the Adam branch reads the row too (split_train.hip's bodies); else
 // its scalars arrive in adam_sc, read before the gradient sums (split_lanes_body).  GUARD:
 // only the slots with slot[k] >= 0 update (split_stage_body_v1, whose unowned slots have no
-// sink to store to).
+// sink to store to).  t: the step counter before this step (AdamW's rate: decoupled_decay_step).
 template <bool ROW_LATE, bool GUARD, int NPT>
 DTP_DEV void split_optim_step(const DtpHyper& hp, bool adam, float2 adam_sc, const float2 (&tab)[kSplitAdamTab], int it,
-                              bool first_step, float gs, const int (&slot)[NPT], float (&pw)[NPT], float (&mr)[NPT],
+                              int t, bool first_step, float gs, const int (&slot)[NPT], float (&pw)[NPT], float (&mr)[NPT],
                               float (&vr)[NPT], const float (&g)[NPT]) {
   if (adam) {
     AdamScalars as = adam_consts(hp);
@@ -41,6 +41,7 @@ DTP_DEV void split_optim_step(const DtpHyper& hp, bool adam, float2 adam_sc, con
       as.step_size = adam_sc.x;
       as.bc2_sqrt = adam_sc.y;
     }
+    decoupled_decay_step(hp, as, t, pw);  // AdamW: p *= d_t (every slot: the unowned ones are never stored)
 #pragma unroll
     for (int k = 0; k < NPT; ++k)
       if (!GUARD || slot[k] >= 0) adam_update(pw[k], mr[k], vr[k], g[k] * gs, as);

@@ -590,7 +590,7 @@ DTP_DEV void split_lanes_body(const DtpSplitStageArgs& a, unsigned char* smem, i
     }
     // ---------------- optimizer (registers) + weight refresh (LDS)
     const float gs = a.hp.grad_scale;
-    split_optim_step<false, false>(a.hp, adam, adam_sc, sm.adam_tab, it, t == 0, gs, pf, pw, mr, vr, g);
+    split_optim_step<false, false>(a.hp, adam, adam_sc, sm.adam_tab, it, t, t == 0, gs, pf, pw, mr, vr, g);
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
       const float wv = S::rnd(pw[k]);

@@ -50,6 +50,8 @@ inline int split_check_stage(const DtpSplitStageArgs& a, const SplitShape& sh, c
   if (a.n_steps <= 0) return refuse("n_steps must be positive");
   if (a.optim != DTP_MODE_ADAM && a.optim != DTP_MODE_SGD) return refuse("adam or sgd");
   if (a.optim == DTP_MODE_ADAM && !a.opt_v) return refuse("Adam needs opt_v");
+  if (a.hp.decoupled_wd && a.optim != DTP_MODE_ADAM)
+    return refuse("decoupled weight decay (AdamW) is Adam's: SGD has no decoupled form");
   if (first && !a.X) return refuse("the first stage needs the inputs");
   if (last && !a.Y) return refuse("the last stage needs the targets");
   if (!first && (!a.act_in || !a.grad_out)) return refuse("missing links to the previous stage");

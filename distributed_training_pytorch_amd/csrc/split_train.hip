@@ -316,7 +316,7 @@ DTP_DEV void split_stage_body_v1(const DtpSplitStageArgs& a, unsigned char* smem
 
     // ---- optimizer (registers) + weight refresh (LDS)
     const float gs = a.hp.grad_scale;
-    split_optim_step<true, true>(a.hp, adam, float2{}, sm.adam_tab, it, t == 0, gs, lp, pw, mr, vr, g);
+    split_optim_step<true, true>(a.hp, adam, float2{}, sm.adam_tab, it, t, t == 0, gs, lp, pw, mr, vr, g);
 #pragma unroll
     for (int k = 0; k < NPT; ++k) {
       if (lp[k] >= 0) sm.w[lp[k]] = pw[k];
@@ -633,7 +633,7 @@ DTP_DEV void split_stage_body_pipe(const DtpSplitStageArgs& a, unsigned char* sm
     SPLIT_STAMP(7);
     // ---- optimizer (registers) + weight refresh (LDS)
     const float gs = a.hp.grad_scale;
-    split_optim_step<true, false>(a.hp, adam, float2{}, sm.adam_tab, it, t == 0, gs, pfl, pw, mr, vr, g);
+    split_optim_step<true, false>(a.hp, adam, float2{}, sm.adam_tab, it, t, t == 0, gs, pfl, pw, mr, vr, g);
     scatter();
     if constexpr (LAST) {
       const int owner = use_dp ? xgmi_loss_tid<NPT>(P, kBlock) : 0;

@@ -267,6 +267,10 @@ def train(config, env, device, rank, world, group: str = "base-demo") -> dict:
     wall = time.perf_counter() - t_start
     logger.finish()
     summary["wall_s"] = wall
+    # what ran: the stock loop keeps the reference's verbatim Adam(lr=1e-3) pair unless the run
+    # asks for AdamW (it ignores --optimizer sgd, --lr and --weight_decay otherwise)
+    summary["optimizer"] = "adam" if summary.get("engine") == "stock" and config.optimizer != "adamw" \
+        else _optim(config).label
     summary.update(_lr_summary(config, int(summary.get("iters", 0))))
     rank_print(rank, "Finished")
     return summary
@@ -687,7 +691,9 @@ def _train_stock(config, device, rank, world, logger, faults) -> dict:
     ds = _dataset(config, rank)
     loop = StockLoop(ds, device, batch=config.batch_size, seed=config.seed,
                      clip_grad_norm=_clip_norm(config), clip_grad_value=_clip_value(config),
-                     schedule=lr_schedule(config), accumulate=_accumulate(config))
+                     schedule=lr_schedule(config), accumulate=_accumulate(config),
+                     # the verbatim Adam(lr=1e-3) pair unless the run asks for AdamW
+                     optim=_optim(config) if config.optimizer == "adamw" else None)
     pbar = _progress(rank, config.iters, config)
     timer = PhaseTimer(device)
     val = _Validation(config, ds, rank, world, device, logger)

@@ -18,7 +18,7 @@ from .schedule import LrSchedule, lr_at
 
 @dataclass
 class OptimConfig:
-    name: str = "adam"  # "adam" | "sgd"
+    name: str = "adam"  # "adam" | "sgd"; "adamw" is stored as "adam" with decoupled_weight_decay
     lr: float = 1e-3
     betas: tuple[float, float] = (0.9, 0.999)
     eps: float = 1e-8
@@ -29,14 +29,28 @@ class OptimConfig:
     clip_grad_value: float = 0.0  # > 0: torch.nn.utils.clip_grad_value_(row, clip_grad_value)
     # the rate of every step (ops.schedule); None: ``lr`` at every step
     schedule: LrSchedule | None = None
+    # torch.optim.AdamW = Adam(decoupled_weight_decay=True): p *= 1 - lr_t * weight_decay ahead
+    # of Adam's update, and weight_decay enters neither the gradient nor m / v.  Adam only.
+    decoupled_weight_decay: bool = False
 
     def __post_init__(self):
+        if self.name == "adamw":
+            self.name = "adam"
+            self.decoupled_weight_decay = True
+        self.decoupled_weight_decay = bool(self.decoupled_weight_decay)
+        if self.decoupled_weight_decay and self.name != "adam":
+            raise ValueError(f"OptimConfig: decoupled weight decay is AdamW's; {self.name!r} has no decoupled form")
         if self.max_grad_norm > 0 and self.clip_grad_value > 0:
             raise ValueError("OptimConfig: max_grad_norm and clip_grad_value are exclusive (one clipping algorithm)")
 
     @property
     def clips(self) -> bool:
         return self.max_grad_norm > 0 or self.clip_grad_value > 0
+
+    @property
+    def label(self) -> str:
+        """The optimizer's name for logs and run summaries: "adamw" | "adam" | "sgd"."""
+        return "adamw" if self.name == "adam" and self.decoupled_weight_decay else self.name
 
     @property
     def kind(self) -> int:
@@ -51,6 +65,7 @@ class OptimConfig:
         runs: the table lives there (cached by the schedule, which this config keeps alive)."""
         hp = nat.Hyper(self.lr, self.betas[0], self.betas[1], self.eps, self.weight_decay, self.momentum,
                        slope, grad_scale)
+        hp.decoupled_wd = 1 if self.decoupled_weight_decay else 0
         if self.schedule is not None:
             if device is None:
                 raise ValueError("OptimConfig.hyper: a schedule needs the device of the launch")
@@ -64,6 +79,9 @@ class OptimConfig:
         return lr_at(self, t)
 
     def torch_optimizer(self, params):
+        if self.name == "adam" and self.decoupled_weight_decay:
+            return torch.optim.AdamW(params, lr=self.lr, betas=self.betas, eps=self.eps,
+                                     weight_decay=self.weight_decay)
         if self.name == "adam":
             return torch.optim.Adam(params, lr=self.lr, betas=self.betas, eps=self.eps,
                                     weight_decay=self.weight_decay)
@@ -76,7 +94,10 @@ def adam_update_ref(p: torch.Tensor, m: torch.Tensor, v: torch.Tensor, g: torch.
     is that of the step taken after t1 - 1 steps."""
     b1, b2 = cfg.betas
     if cfg.weight_decay:
-        g = g + cfg.weight_decay * p
+        if cfg.decoupled_weight_decay:  # AdamW: the factor in float64, one multiply in p's dtype
+            p.mul_(1 - cfg.lr_at(t1 - 1) * cfg.weight_decay)
+        else:
+            g = g + cfg.weight_decay * p
     m.lerp_(g, 1 - b1)
     v.mul_(b2).addcmul_(g, g, value=1 - b2)
     bc1 = 1 - b1 ** t1
