@@ -181,10 +181,34 @@ def test_bench_weak_scaling_flag_share_gpu():
     assert rec["config"]["per_rank_batch"] == 256 and rec["config"]["dataset_samples"] == 1024
 
 
+_CU_MASK_PROBE = """
+import sys, torch
+from distributed_training_pytorch_amd import _native
+try:
+    _native.cu_masked_stream(torch.device("cuda", 0), [0, 1])
+except RuntimeError as e:
+    print(e)
+    sys.exit(3 if "hipExtStreamCreateWithCUMask" in str(e) and "out of memory" in str(e) else 1)
+"""
+
+
+def _cu_masked_streams_unsupported() -> bool:
+    """True where the HIP runtime cannot make a CU-masked stream at all (seen on an
+    MI355X passed through to a virtual machine): ``hipExtStreamCreateWithCUMask`` of the
+    valid mask {0, 1} returns hipErrorOutOfMemory there, HIP's code for "the stream's
+    hardware queue could not be made".  Asked in a process of its own, so the failed call leaves no HIP error behind
+    in this one.  Any other outcome (success, another error, a crash) is False: the test
+    runs and reports it."""
+    r = subprocess.run([sys.executable, "-c", _CU_MASK_PROBE], cwd=ROOT, capture_output=True, text=True, timeout=110)
+    return r.returncode == 3
+
+
 def test_bench_cu_mask_keeps_split_batch_resident():
     """--cu-mask on pins the step to 2 CUs: the split-batch step (8 x 4 co-resident
     workgroups spinning on each other) cannot run there, so the engine refuses it and
     runs the one-workgroup-per-model step instead of timing out."""
+    if _cu_masked_streams_unsupported():
+        pytest.skip("hipExtStreamCreateWithCUMask is not supported here (CU-masked streams cannot be created)")
     r = subprocess.run([sys.executable, "bench.py", "--cu-mask", "on", "--steps", "50", "--warmup", "5"],
                        cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-2000:]
