@@ -236,6 +236,32 @@ class GemmArgs(ctypes.Structure):
     ]
 
 
+class GemmFp8Args(ctypes.Structure):
+    _fields_ = [
+        ("A", c_void_p),
+        ("B", c_void_p),
+        ("C", c_void_p),
+        ("bias", c_void_p),
+        ("aux", c_void_p),
+        ("sa_inv", c_void_p),
+        ("sb_inv", c_void_p),
+        ("lda", c_longlong),
+        ("ldb", c_longlong),
+        ("ldc", c_longlong),
+        ("ldaux", c_longlong),
+        ("M", c_int),
+        ("N", c_int),
+        ("K", c_int),
+        ("fmt_a", c_int),
+        ("fmt_b", c_int),
+        ("out_dtype", c_int),
+        ("act", c_int),
+        ("accumulate", c_int),
+        ("slope", c_float),
+        ("mfma", c_int),
+    ]
+
+
 class EvalArgs(ctypes.Structure):
     _fields_ = [
         ("X", c_void_p),
@@ -254,6 +280,8 @@ class EvalArgs(ctypes.Structure):
 
 
 DT_F32, DT_BF16 = 0, 1
+FP8_E4M3, FP8_E5M2 = 0, 1
+FP8_WS_FLOATS = 1026  # DTP_FP8_WS_FLOATS: scale, 1 / scale, the amax partials
 MODE_GRAD, MODE_ADAM, MODE_SGD, MODE_XGMI_ADAM, MODE_XGMI_SGD = 0, 1, 2, 3, 4
 LOSS_MSE, LOSS_CE = 0, 1
 SAMPLER_EXPLICIT, SAMPLER_DIST_SHUFFLE, SAMPLER_SEQUENTIAL, SAMPLER_DIST_NOSHUFFLE, SAMPLER_TABLE = 0, 1, 2, 3, 4
@@ -356,6 +384,9 @@ def _declare(lib):
                                        c_void_p, c_int, c_void_p]),
         "dtp_xgmi_allreduce_epoch_slots": (c_int, [c_int]),
         "dtp_colsum": (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+        "dtp_fp8_quantize": (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p,
+                                     c_longlong, c_void_p, c_void_p]),
+        "dtp_gemm_fp8": (c_int, [P(GemmFp8Args), c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -44,7 +44,11 @@ STEP_SOURCES = ("mlp_train.hip", "mlp_train_one.hip", "mlp_train_lanes.hip", "ml
                 "mlp_train_lanes_accum.hip")
 SOURCE_FLAGS = {**{s: ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contract=off"] for s in STEP_SOURCES},
                 "optim.hip": ["-ffp-contract=off"],
-                "split_train.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contract=off"]}
+                "split_train.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contract=off"],
+                # the FP8 sources: no packed-fp32 VALU forms (v_pk_mul_f32 and kin) in the scale /
+                # epilogue math, so the quantiser rounds exactly as its torch definition does
+                **{s: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+                   for s in ("fp8_quant.hip", "gemm_fp8.hip")}}
 
 
 def hipcc() -> str:

@@ -280,6 +280,37 @@ long long dtp_gemm_workspace(const DtpGemmArgs* a);
 // out[n] (+)= sum_m X[m*ld+n]  (bias gradients)
 int dtp_colsum(const void* X, long long ld, int M, int N, int dtype, float* out, int accumulate, void* stream);
 
+// ---- FP8 (OCP e4m3 / e5m2) quantiser and GEMM (fp8_quant.hip, gemm_fp8.hip) ----
+#define DTP_FP8_E4M3 0
+#define DTP_FP8_E5M2 1
+#define DTP_FP8_WS_FLOATS 1026  // workspace of dtp_fp8_quantize: scale, 1 / scale, 1024 amax partials
+// Per-tensor scaled cast: ws[0] = fmax(fmt) / amax|x| (1 for an all-zero x), ws[1] = 1 / ws[0],
+// q[m*ldq+k] = cvt(x[m*ldx+k] * ws[0]) and, with qT, qT[k*ldt+m] likewise.  x is f32 or bf16
+// (DTP_DT_*), K % 16 == 0, ldq % 16 == 0, ldt % 16 == 0 and ldt >= M rounded up to 16 (the
+// columns of qT past M are written as zeros).  Two launches, no host read.
+int dtp_fp8_quantize(const void* x, long long ldx, int M, int K, int dtype, int fmt, void* q, long long ldq,
+                     void* qT, long long ldt, float* ws, void* stream);
+
+struct DtpGemmFp8Args {
+  const void* A;        // [M][lda] fp8 (fmt_a), K-contiguous
+  const void* B;        // [N][ldb] fp8 (fmt_b), K-contiguous
+  void* C;              // [M][ldc], out_dtype
+  const float* bias;    // [N] or null
+  const void* aux;      // [M][ldaux] bf16 or null: multiply by LeakyReLU'(aux)
+  const float* sa_inv;  // device scalars: the operands' inverse scales
+  const float* sb_inv;
+  long long lda, ldb, ldc, ldaux;
+  int M, N, K;          // K % 16 == 0; bytes of a row past K up to the next multiple of 16 are never read
+  int fmt_a, fmt_b;     // DTP_FP8_*: e4m3 x e4m3 or e5m2 x e4m3
+  int out_dtype;        // DTP_DT_* of C
+  int act;              // 1: LeakyReLU(slope) on the result
+  int accumulate;       // 1: C += result
+  float slope;
+  int mfma;             // matrix instruction: 0 the 16x16x128 f8f6f4 MFMA, 1 the 16x16x32 fp8 / bf8 MFMAs
+};
+// C[M,N] (+)= epilogue(sa_inv * sb_inv * A(m,:) . B(n,:)), fp32 accumulation, the epilogues of dtp_gemm
+int dtp_gemm_fp8(const DtpGemmFp8Args* a, void* stream);
+
 // sampler probe (tests): dataset indices of steps [t0, t0+n_steps), row-major [n_steps][batch], -1 padded
 int dtp_sampler_indices(const dtp::SamplerCfg* s, long long t0, int n_steps, int* out, void* stream);
 

@@ -88,13 +88,23 @@ def _geom(config, rank, world):
 
 
 def _compute_dtype(config) -> torch.dtype:
-    return torch.bfloat16 if getattr(config, "precision", "fp32") == "bf16" else torch.float32
+    precision = getattr(config, "precision", "fp32")
+    if precision == "fp8":
+        if config.hidden % 16:
+            # the FP8 GEMM reads 16-byte operand rows; a narrower hidden width would leave every
+            # layer on the bf16 kernels, which is not what the flag asks for
+            raise ValueError(f"--precision fp8 needs --hidden to be a multiple of 16 (got {config.hidden}): a Linear "
+                             "runs on the FP8 GEMM only if both its widths are multiples of 16")
+        return torch.float8_e4m3fn
+    return torch.bfloat16 if precision == "bf16" else torch.float32
 
 
 def _fused_supported(config) -> bool:
     from .. import _native as nat
     from ..ops.mlp import MlpSpec
 
+    if _compute_dtype(config) == torch.float8_e4m3fn:  # FP8 lives on the module engine's GEMM layers
+        return False
     spec = MlpSpec(2, config.hidden, config.depth + 2, 4 if config.loss == "ce" else 1)
     if _compute_dtype(config) == torch.bfloat16:
         try:
@@ -237,7 +247,8 @@ def train(config, env, device, rank, world, group: str = "base-demo") -> dict:
     faults = FaultInjector(config.fail_at_iter, config.fail_rank, rank)
     t_start = time.perf_counter()
     engine = config.engine
-    if engine == "fused" and device.type == "cuda" and not _fused_supported(config):
+    fp8 = _compute_dtype(config) == torch.float8_e4m3fn  # (raises on a width the FP8 path cannot take)
+    if engine == "fused" and (device.type == "cuda" or fp8) and not _fused_supported(config):
         # widths / dtypes the fused step kernel is not instantiated for train through
         # nn.Modules whose Linears run on the MFMA GEMM (FlatDDP + FlatOptimizer)
         rank_print(rank, f"fused step kernel has no instance for hidden={config.hidden} depth={config.depth} "

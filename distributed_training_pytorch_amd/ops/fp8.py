@@ -1,0 +1,226 @@
+"""FP8 operands for the wide-MLP GEMM path: the per-tensor quantiser
+(``csrc/fp8_quant.hip``) and the FP8 GEMM (``csrc/gemm_fp8.hip``).
+
+The hybrid recipe: e4m3 for activations and weights, e5m2 for the gradients flowing
+back, fp32 accumulation, one scale per tensor from the tensor's current amax
+(``scale = fmax / amax``, formed and kept on the device: nothing here reads the GPU
+back, so a step can be captured into a hipGraph).  gfx950's formats are the OCP ones,
+``torch.float8_e4m3fn`` and ``torch.float8_e5m2``.
+
+The GEMM only takes K-contiguous operands, so the quantiser also writes the transposed
+copy when asked (one launch reads ``x`` once and writes both).
+
+On CPU tensors both ops run the torch definition of the same math; on a GPU the HIP
+kernels are required.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import torch
+
+from .. import _native as nat
+from .gemm import _DT, _ld, _ref
+
+_MFMA = 0  # the kernel's matrix instruction: 0 = 16x16x128 f8f6f4, 1 = 16x16x32 fp8 / bf8
+_FMT = {"e4m3": (torch.float8_e4m3fn, 448.0, nat.FP8_E4M3), "e5m2": (torch.float8_e5m2, 57344.0, nat.FP8_E5M2)}
+
+
+class Fp8Tensor(NamedTuple):
+    data: torch.Tensor            # [M, K] fp8
+    data_t: torch.Tensor | None   # [K, M] fp8: a view of rows padded with zeros to a multiple of 16
+    scale: torch.Tensor           # fp32 scalar on the tensor's device: data = cvt(x * scale)
+    scale_inv: torch.Tensor       # 1 / scale
+    fmt: str
+
+
+def quantize_fp8(x: torch.Tensor, fmt: str = "e4m3", transpose: bool = False) -> Fp8Tensor:
+    """``cvt(x * scale)`` with ``scale = fmax(fmt) / amax|x|`` (1 for an all-zero ``x``), round to
+    nearest even; ``x`` is [M, K] fp32 or bf16 with K a multiple of 16."""
+    if fmt not in _FMT:
+        raise ValueError(f"quantize_fp8: fmt {fmt!r} not in {sorted(_FMT)}")
+    if x.dim() != 2 or x.dtype not in _DT or x.shape[1] % 16 or 0 in x.shape:
+        raise ValueError(f"quantize_fp8: x must be a non-empty fp32 / bf16 [M, K] with K a multiple of 16, got "
+                         f"{x.dtype} {tuple(x.shape)}")
+    dtype, fmax, code = _FMT[fmt]
+    M, K = x.shape
+    Mp = -(-M // 16) * 16
+    if x.device.type != "cuda" or not nat.native_enabled():
+        amax = x.detach().abs().max().float()
+        # tensor / tensor: one correctly rounded fp32 division, as the kernel's (a python scalar
+        # over a tensor is reciprocal-then-multiply, two roundings)
+        scale = torch.where(amax > 0, torch.full_like(amax, fmax) / amax, torch.ones_like(amax))
+        q = (x.detach().float() * scale).to(dtype)
+        qt = None
+        if transpose:
+            qt = torch.zeros(K, Mp, dtype=dtype)
+            qt[:, :M] = q.t()
+            qt = qt[:, :M]
+        return Fp8Tensor(q, qt, scale, torch.ones_like(scale) / scale, fmt)
+    lib = nat.require(x.device)
+    x = x.detach()
+    if x.stride(1) != 1:
+        x = x.contiguous()  # (rows that are not 16-byte aligned are fine: the kernel then loads by element)
+    q = torch.empty(M, K, dtype=dtype, device=x.device)
+    qt = torch.empty(K, Mp, dtype=dtype, device=x.device) if transpose else None
+    ws = torch.empty(nat.FP8_WS_FLOATS, dtype=torch.float32, device=x.device)
+    nat.check(lib.dtp_fp8_quantize(nat.ptr(x), _ld(x, "x"), M, K, _DT[x.dtype], code, nat.ptr(q), K, nat.ptr(qt), Mp,
+                                   nat.ptr(ws), nat.stream_ptr()), "dtp_fp8_quantize")
+    return Fp8Tensor(q, None if qt is None else qt[:, :M], ws[0], ws[1], fmt)
+
+
+def _operand(t: Fp8Tensor, trans: bool, name: str) -> torch.Tensor:
+    d = t.data_t if trans else t.data
+    if d is None:
+        raise ValueError(f"gemm_fp8: {name} was quantised without its transposed copy")
+    return d
+
+
+def gemm_fp8(a: Fp8Tensor, b: Fp8Tensor, *, trans_a: bool = False, trans_b: bool = False,
+             bias: torch.Tensor | None = None, aux: torch.Tensor | None = None, act: bool = False, slope: float = 0.01,
+             out: torch.Tensor | None = None, accumulate: bool = False,
+             out_dtype: torch.dtype | None = None, mfma: int = _MFMA) -> torch.Tensor:
+    """C[M,N] (+)= epilogue(a.scale_inv * b.scale_inv * A(m,k) B(n,k)), fp32 accumulation.
+
+    A is ``a.data`` [M,K] (``a.data_t`` with ``trans_a``), B is ``b.data`` [N,K] (``b.data_t`` with
+    ``trans_b``): e4m3 x e4m3 or e5m2 x e4m3.  Epilogue order as ``gemm``: + bias[n],
+    * LeakyReLU'(aux[m,n]) (aux bf16), LeakyReLU, (+ old C), cast to bf16 or fp32."""
+    A, B = _operand(a, trans_a, "a"), _operand(b, trans_b, "b")
+    (M, K), (N, Kb) = A.shape, B.shape
+    if K != Kb:
+        raise ValueError(f"gemm_fp8: inner dimensions differ ({K} vs {Kb})")
+    if b.fmt != "e4m3":
+        raise ValueError("gemm_fp8: operand formats are e4m3 x e4m3 or e5m2 x e4m3")
+    out_dtype = out_dtype or (out.dtype if out is not None else torch.bfloat16)
+    if out_dtype not in _DT:
+        raise ValueError(f"gemm_fp8: out dtype must be float32 or bfloat16, got {out_dtype}")
+    if out is None:
+        out = (torch.zeros if accumulate else torch.empty)(M, N, dtype=out_dtype, device=A.device)
+    if out.shape != (M, N) or out.dtype != out_dtype:
+        raise ValueError(f"gemm_fp8: out must be [{M},{N}] {out_dtype}")
+    if aux is not None and (aux.shape != (M, N) or aux.dtype != torch.bfloat16):
+        raise ValueError("gemm_fp8: aux must be a bf16 [M,N]")
+    if A.device.type != "cuda" or not nat.native_enabled():
+        r = _ref(A.float(), B.float(), False, False, bias, aux, act, slope, a.scale_inv * b.scale_inv)
+        if accumulate:
+            r = r + out.float()
+        out.copy_(r.to(out_dtype))
+        return out
+    lib = nat.require(A.device)
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
+        bias = bias.float().contiguous()
+    # a transposed copy's rows are padded with zeros to 16 bytes: the kernel sums over the padded K
+    Kp = -(-K // 16) * 16
+    if Kp != K and not (trans_a and trans_b):
+        raise ValueError(f"gemm_fp8: K = {K} is not a multiple of 16 (only two transposed copies carry the padding)")
+    args = nat.GemmFp8Args()
+    args.A, args.B, args.C = nat.ptr(A), nat.ptr(B), nat.ptr(out)
+    args.bias, args.aux = nat.ptr(bias), nat.ptr(aux)
+    args.sa_inv, args.sb_inv = nat.ptr(a.scale_inv), nat.ptr(b.scale_inv)
+    args.lda, args.ldb, args.ldc = max(_ld(A, "a"), Kp), max(_ld(B, "b"), Kp), _ld(out, "out")
+    args.ldaux = _ld(aux, "aux") if aux is not None else 0
+    args.M, args.N, args.K = M, N, Kp
+    args.fmt_a, args.fmt_b = _FMT[a.fmt][2], _FMT[b.fmt][2]
+    args.out_dtype = _DT[out_dtype]
+    args.act, args.accumulate, args.slope = int(act), int(accumulate), float(slope)
+    args.mfma = int(mfma)
+    nat.check(lib.dtp_gemm_fp8(args, nat.stream_ptr()), "dtp_gemm_fp8")
+    return out
+
+
+# ------------------------------------------------------------------ MLPFunction with fp8 compute
+def fp8_layer(w: torch.Tensor) -> bool:
+    """A Linear runs on the FP8 GEMM only if both its widths are multiples of 16 (16-byte
+    operand rows); any other layer of the same model stays on the bf16 kernels."""
+    return w.shape[0] % 16 == 0 and w.shape[1] % 16 == 0
+
+
+def mlp_fp8_forward(ctx, x, slope, params):
+    """``MLPFunction.forward`` for ``compute_dtype=torch.float8_e4m3fn``: per FP8 layer the weight
+    (from its fp32 master) and the input activation are quantised to e4m3 once, each with its
+    transposed copy for the backward; the GEMM writes the bf16 activation (the backward's aux)."""
+    from .gemm import _compute_weight, gemm
+
+    weights, biases = params[0::2], params[1::2]
+    L, cd = len(weights), torch.bfloat16
+    h = x.detach().to(cd).contiguous()
+    hs, saved, kinds = [h], [], []
+    for l in range(L):
+        last = l == L - 1
+        out_dtype = torch.float32 if last else cd
+        if fp8_layer(weights[l]):
+            wq = quantize_fp8(weights[l], "e4m3", transpose=True)
+            hq = quantize_fp8(h, "e4m3", transpose=True)
+            h = gemm_fp8(hq, wq, bias=biases[l].detach(), act=not last, slope=slope, out_dtype=out_dtype)
+            saved += [hq.data_t, hq.scale_inv, wq.data_t, wq.scale_inv]
+            kinds.append(True)
+        else:
+            w = _compute_weight(weights[l], cd)
+            h = gemm(h, w, bias=biases[l].detach(), act=not last, slope=slope, out_dtype=out_dtype)
+            saved.append(w)
+            kinds.append(False)
+        if not last:
+            hs.append(h)
+    ctx.save_for_backward(*hs, *saved)
+    ctx.params = [q if q.is_leaf else None for q in params]
+    ctx.L, ctx.slope, ctx.x_dtype, ctx.kinds = L, slope, x.dtype, kinds
+    ctx.x_needs = ctx.needs_input_grad[0]
+    return h
+
+
+def mlp_fp8_backward(ctx, gy):
+    """dz is quantised to e5m2 (row-major for dx = dz W, transposed for dW = dz^T h); both GEMMs
+    run e5m2 x e4m3 on the copies the forward saved.  Bias gradients read the bf16 dz."""
+    from .gemm import _fused_grad_target, _grad_ready, colsum, gemm
+
+    L, slope, cd = ctx.L, ctx.slope, torch.bfloat16
+    saved = list(ctx.saved_tensors)
+    hs, rest = saved[:L], saved[L:]
+    per_layer = []
+    for k in ctx.kinds:
+        n = 4 if k else 1
+        per_layer.append(rest[:n])
+        rest = rest[n:]
+    dz = gy.to(cd).contiguous()
+    gW: list[torch.Tensor | None] = [None] * L
+    gb: list[torch.Tensor | None] = [None] * L
+    dx = None
+    need = ctx.needs_input_grad[3:]
+    for l in range(L - 1, -1, -1):
+        pw, pb = ctx.params[2 * l], ctx.params[2 * l + 1]
+        tw = _fused_grad_target(pw) if (pw is not None and need[2 * l]) else None
+        tb = _fused_grad_target(pb) if (pb is not None and need[2 * l + 1]) else None
+        if ctx.kinds[l]:
+            h_t, h_sinv, w_t, w_sinv = per_layer[l]
+            dq = quantize_fp8(dz, "e5m2", transpose=True)
+            hT = Fp8Tensor(None, h_t, None, h_sinv, "e4m3")
+            wT = Fp8Tensor(None, w_t, None, w_sinv, "e4m3")
+            if tw is not None:  # dW += dz^T h in the GEMM epilogue
+                gemm_fp8(dq, hT, trans_a=True, trans_b=True, out=tw, accumulate=True)
+            else:
+                gW[l] = gemm_fp8(dq, hT, trans_a=True, trans_b=True, out_dtype=torch.float32)
+        elif tw is not None:
+            gemm(dz, hs[l], trans_a=True, trans_b=True, out=tw, accumulate=True)
+        else:
+            gW[l] = gemm(dz, hs[l], trans_a=True, trans_b=True, out_dtype=torch.float32)
+        if tb is not None:
+            colsum(dz, out=tb, accumulate=True)
+        else:
+            gb[l] = colsum(dz)
+        for q, t in ((pw, tw), (pb, tb)):
+            if t is not None:
+                _grad_ready(q)
+        if l > 0 or ctx.x_needs:
+            kw = dict(aux=hs[l], slope=slope, out_dtype=cd) if l > 0 else dict(out_dtype=torch.float32)
+            if ctx.kinds[l]:
+                r = gemm_fp8(dq, wT, trans_b=True, **kw)
+            else:
+                r = gemm(dz, per_layer[l][0], trans_b=True, **kw)
+            if l > 0:
+                dz = r
+            else:
+                dx = r.to(ctx.x_dtype)
+    grads = []
+    for l in range(L):
+        grads += [gW[l], gb[l]]
+    return (dx, None, None, *grads)

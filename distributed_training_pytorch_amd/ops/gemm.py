@@ -256,11 +256,18 @@ class MLPFunction(torch.autograd.Function):
 
     ``compute_dtype`` bf16 = autocast-style mixed precision: fp32 master weights
     cast once per forward, bf16 activations, fp32 accumulation and fp32 weight /
-    bias gradients; fp32 = exact-fp32 MFMA throughout.
+    bias gradients; fp32 = exact-fp32 MFMA throughout; ``torch.float8_e4m3fn`` = the
+    bf16 recipe with every layer whose widths are multiples of 16 on the FP8 GEMM
+    (``ops/fp8.py``: e4m3 activations and weights, e5m2 gradients, per-tensor scales).
     """
 
     @staticmethod
     def forward(ctx, x, slope, compute_dtype, *params):
+        ctx.fp8 = compute_dtype == torch.float8_e4m3fn
+        if ctx.fp8:  # FP8 layer GEMMs with per-tensor scales (ops/fp8.py)
+            from .fp8 import mlp_fp8_forward
+
+            return mlp_fp8_forward(ctx, x, slope, params)
         weights, biases = params[0::2], params[1::2]
         L = len(weights)
         ws = [_compute_weight(w, compute_dtype) for w in weights]
@@ -281,6 +288,10 @@ class MLPFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
+        if ctx.fp8:
+            from .fp8 import mlp_fp8_backward
+
+            return mlp_fp8_backward(ctx, gy)
         L, slope = ctx.L, ctx.slope
         saved = ctx.saved_tensors
         hs, ws = saved[:L], saved[L:]

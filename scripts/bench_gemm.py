@@ -43,7 +43,48 @@ def case(M, N, K, ta, tb, dtype, iters):
             "torch_ms": round(theirs, 4), "torch_tflops": round(fl / theirs / 1e9, 1), "max_abs_err": err}
 
 
+def fp8_layers(widths, batch, rounds, iters):
+    """--fp8: the three layer GEMMs of a W-wide Linear at bench_wide.py's batch (forward, dx, dW)
+    on the FP8 kernel, both matrix instructions (f8f6f4 16x16x128 / fp8 16x16x32), interleaved
+    with the bf16 kernels of the same build in one process: `rounds` rounds, medians.  Then the
+    quantiser alone: GB/s against the bytes it moves (x read, q and qT written)."""
+    from distributed_training_pytorch_amd.ops.fp8 import gemm_fp8, quantize_fp8
+
+    def rnd(*shape):
+        return torch.rand(*shape, device=DEV) * 2 - 1
+
+    for W in widths:
+        h, w, dz = rnd(batch, W).bfloat16(), rnd(W, W), rnd(batch, W).bfloat16()
+        wb = w.bfloat16()
+        hq, wq, dq = (quantize_fp8(h, "e4m3", True), quantize_fp8(w, "e4m3", True), quantize_fp8(dz, "e5m2", True))
+        bias, dwf = rnd(W), torch.zeros(W, W, device=DEV)
+        fns = {"fwd": {"bf16": lambda: gemm(h, wb, bias=bias, act=True)},
+               "dx": {"bf16": lambda: gemm(dz, wb, trans_b=True, aux=h)},
+               "dW": {"bf16": lambda: gemm(dz, h, trans_a=True, trans_b=True, out=dwf, accumulate=True)}}
+        for m, tag in ((0, "fp8_x128"), (1, "fp8_x32")):
+            fns["fwd"][tag] = lambda m=m: gemm_fp8(hq, wq, bias=bias, act=True, mfma=m)
+            fns["dx"][tag] = lambda m=m: gemm_fp8(dq, wq, trans_b=True, aux=h, mfma=m)
+            fns["dW"][tag] = lambda m=m: gemm_fp8(dq, hq, trans_a=True, trans_b=True, out=dwf, accumulate=True, mfma=m)
+        for name, impls in fns.items():
+            ms = {k: [] for k in impls}
+            for _ in range(rounds):
+                for k, fn in impls.items():
+                    ms[k].append(timeit(fn, iters))
+            med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+            fl = 2.0 * batch * W * W
+            print(json.dumps({"gemm": name, "W": W, "batch": batch, "rounds": rounds,
+                              **{f"{k}_ms": round(v, 4) for k, v in med.items()},
+                              **{f"{k}_tflops": round(fl / v / 1e9, 1) for k, v in med.items()}}), flush=True)
+        for x, fmt in ((h, "e4m3"), (w, "e4m3"), (dz, "e5m2")):
+            t = sorted(timeit(lambda: quantize_fp8(x, fmt, True), iters) for _ in range(rounds))[rounds // 2]
+            nbytes = x.numel() * (x.element_size() + 2)
+            print(json.dumps({"quantize": fmt, "shape": list(x.shape), "in": str(x.dtype), "ms": round(t, 4),
+                              "GB_per_s": round(nbytes / t / 1e6, 1)}), flush=True)
+
+
 def main():
+    if "--fp8" in sys.argv:
+        return fp8_layers((1024, 2048, 4096), 8192, 5, 10)
     cases = [(4096, 4096, 4096), (8192, 8192, 8192), (8192, 4096, 4096), (16384, 1024, 1024)]
     dtypes = ((torch.bfloat16, 20),) if "--bf16" in sys.argv else ((torch.bfloat16, 20), (torch.float32, 5))
     for dtype, its in dtypes:

@@ -37,7 +37,8 @@ def run_ours(a, X, Y, dev, world):
     from distributed_training_pytorch_amd.parallel.ddp import FlatDDP
 
     torch.manual_seed(0)
-    bank = ModelBank(2, hidden=a.width, depth=a.depth, compute_dtype=torch.bfloat16).to(dev)
+    cd = torch.float8_e4m3fn if a.precision == "fp8" else torch.bfloat16
+    bank = ModelBank(2, hidden=a.width, depth=a.depth, compute_dtype=cd).to(dev)
     ddp = FlatDDP(bank, flat_params=bank.flat, flat_grad=bank.flat_grad, comm="rccl") if world > 1 else None
     # --shadow: Adam also writes the bf16 weight operands (no per-forward casts). Measured
     # at W = 4096 / 2048 / 1024: 4.52 / 1.78 / 1.28 ms vs 4.56 / 1.75 / 1.28 casting each
@@ -99,6 +100,9 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--impl", choices=["ours", "stock", "both"], default="both")
+    ap.add_argument("--precision", choices=["bf16", "fp8"], default="bf16",
+                    help="ours: bf16 layer GEMMs, or fp8 (ops/fp8.py: e4m3 x e4m3 forward, e5m2 x e4m3 backward, "
+                         "per-tensor scales; the hidden width must be a multiple of 16)")
     ap.add_argument("--shadow", action="store_true",
                     help="ours: the Adam kernel writes the bf16 weight operands (ops/gemm.py ComputeShadow) "
                          "instead of a cast before every forward")
@@ -135,7 +139,7 @@ def main():
             print(json.dumps({"impl": impl, "width": a.width, "depth": a.depth, "batch_per_rank": a.batch,
                               "world": world, "ms_per_step": 1e3 * dt / a.steps,
                               "samples_per_s": a.batch * world * a.steps / dt, "model_tflops": flops / dt / 1e12,
-                              "dtype": "bf16 compute, fp32 master weights",
+                              "dtype": f"{a.precision if impl == 'ours' else 'bf16'} compute, fp32 master weights",
                               "gemm_backend": a.gemm_backend if impl == "ours" else "torch",
                               "weight_shadow": a.shadow if impl == "ours" else None}),
                   flush=True)
