@@ -262,6 +262,34 @@ class GemmFp8Args(ctypes.Structure):
     ]
 
 
+class GemmMxArgs(ctypes.Structure):
+    _fields_ = [
+        ("A", c_void_p),
+        ("B", c_void_p),
+        ("C", c_void_p),
+        ("bias", c_void_p),
+        ("aux", c_void_p),
+        ("sa", c_void_p),
+        ("sb", c_void_p),
+        ("lda", c_longlong),
+        ("ldb", c_longlong),
+        ("ldc", c_longlong),
+        ("ldaux", c_longlong),
+        ("ldsa", c_longlong),
+        ("ldsb", c_longlong),
+        ("M", c_int),
+        ("N", c_int),
+        ("K", c_int),
+        ("fmt_a", c_int),
+        ("fmt_b", c_int),
+        ("out_dtype", c_int),
+        ("act", c_int),
+        ("accumulate", c_int),
+        ("slope", c_float),
+        ("instance", c_int),
+    ]
+
+
 class EvalArgs(ctypes.Structure):
     _fields_ = [
         ("X", c_void_p),
@@ -387,6 +415,9 @@ def _declare(lib):
         "dtp_fp8_quantize": (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p,
                                      c_longlong, c_void_p, c_void_p]),
         "dtp_gemm_fp8": (c_int, [P(GemmFp8Args), c_void_p]),
+        "dtp_mxfp8_quantize": (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p,
+                                       c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p]),
+        "dtp_gemm_mxfp8": (c_int, [P(GemmMxArgs), c_void_p]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -48,7 +48,7 @@ SOURCE_FLAGS = {**{s: ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contrac
                 # the FP8 sources: no packed-fp32 VALU forms (v_pk_mul_f32 and kin) in the scale /
                 # epilogue math, so the quantiser rounds exactly as its torch definition does
                 **{s: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-                   for s in ("fp8_quant.hip", "gemm_fp8.hip")}}
+                   for s in ("fp8_quant.hip", "gemm_fp8.hip", "mxfp8_quant.hip", "gemm_mxfp8.hip")}}
 
 
 def hipcc() -> str:

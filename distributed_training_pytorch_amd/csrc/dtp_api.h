@@ -311,6 +311,36 @@ struct DtpGemmFp8Args {
 // C[M,N] (+)= epilogue(sa_inv * sb_inv * A(m,:) . B(n,:)), fp32 accumulation, the epilogues of dtp_gemm
 int dtp_gemm_fp8(const DtpGemmFp8Args* a, void* stream);
 
+// ---- MXFP8: FP8 with one E8M0 scale byte per 32 elements along K (mxfp8_quant.hip, gemm_mxfp8.hip) ----
+// Block-scaled cast of x [M][ldx] (f32 or bf16, K % 32 == 0, finite).  For each block of 32 along K with
+// a = max|x|: scale byte sb = a == 0 ? 127 : max(expfield(a) - emax, 0) (emax 8 e4m3 / 15 e5m2), elements
+// cvt_rne(clamp(x * 2^(127 - sb), -fmax, fmax)).  q [M][ldq] (ldq % 16 == 0), s [M][lds] (lds % 4 == 0,
+// lds >= 4 ceil(K / 128); bytes past K / 32 are written as 127).  With qT: the copy quantised along M,
+// qT [K][ldt] (ldt % 16 == 0, ldt >= Mp = M rounded up to 32; bytes past M up to Mp are zeros) and
+// sT [K][ldst] (as s, for Mp).  One launch, no workspace, no host read.
+int dtp_mxfp8_quantize(const void* x, long long ldx, int M, int K, int dtype, int fmt, void* q, long long ldq, void* s,
+                       long long lds, void* qT, long long ldt, void* sT, long long ldst, void* stream);
+
+struct DtpGemmMxArgs {
+  const void* A;             // [M][lda] fp8 (fmt_a), K-contiguous
+  const void* B;             // [N][ldb] fp8 (fmt_b), K-contiguous
+  void* C;                   // [M][ldc], out_dtype
+  const float* bias;         // [N] or null
+  const void* aux;           // [M][ldaux] bf16 or null: multiply by LeakyReLU'(aux)
+  const unsigned char* sa;   // [M][ldsa] E8M0 bytes: byte kb scales A[m][32 kb .. +32)
+  const unsigned char* sb;   // [N][ldsb]
+  long long lda, ldb, ldc, ldaux, ldsa, ldsb;  // ldsa, ldsb >= 4 ceil(K / 128)
+  int M, N, K;               // K % 32 == 0
+  int fmt_a, fmt_b;          // DTP_FP8_*: e4m3 x e4m3 or e5m2 x e4m3
+  int out_dtype;             // DTP_DT_* of C
+  int act;                   // 1: LeakyReLU(slope) on the result
+  int accumulate;            // 1: C += result
+  float slope;
+  int instance;              // 0: by K; 1: the pipelined block-scaled MFMA kernel; 2: the short-K one (probes)
+};
+// C[M,N] (+)= epilogue(sum_k A(m,k) 2^(sa(m,k/32)-127) B(n,k) 2^(sb(n,k/32)-127)), fp32 accumulation
+int dtp_gemm_mxfp8(const DtpGemmMxArgs* a, void* stream);
+
 // sampler probe (tests): dataset indices of steps [t0, t0+n_steps), row-major [n_steps][batch], -1 padded
 int dtp_sampler_indices(const dtp::SamplerCfg* s, long long t0, int n_steps, int* out, void* stream);
 

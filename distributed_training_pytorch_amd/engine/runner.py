@@ -87,6 +87,9 @@ def _geom(config, rank, world):
                            shuffle=True, distributed=config.dataloader == "distributed", seed=0)
 
 
+_FP8_DTYPES = (torch.float8_e4m3fn, torch.float8_e8m0fnu)
+
+
 def _compute_dtype(config) -> torch.dtype:
     precision = getattr(config, "precision", "fp32")
     if precision == "fp8":
@@ -96,6 +99,12 @@ def _compute_dtype(config) -> torch.dtype:
             raise ValueError(f"--precision fp8 needs --hidden to be a multiple of 16 (got {config.hidden}): a Linear "
                              "runs on the FP8 GEMM only if both its widths are multiples of 16")
         return torch.float8_e4m3fn
+    if precision == "mxfp8":
+        if config.hidden % 32:
+            # an MX block is 32 elements along either contraction of a Linear
+            raise ValueError(f"--precision mxfp8 needs --hidden to be a multiple of 32 (got {config.hidden}): a Linear "
+                             "runs on the MXFP8 GEMM only if both its widths are multiples of 32")
+        return torch.float8_e8m0fnu
     return torch.bfloat16 if precision == "bf16" else torch.float32
 
 
@@ -103,7 +112,7 @@ def _fused_supported(config) -> bool:
     from .. import _native as nat
     from ..ops.mlp import MlpSpec
 
-    if _compute_dtype(config) == torch.float8_e4m3fn:  # FP8 lives on the module engine's GEMM layers
+    if _compute_dtype(config) in _FP8_DTYPES:  # FP8 / MXFP8 live on the module engine's GEMM layers
         return False
     spec = MlpSpec(2, config.hidden, config.depth + 2, 4 if config.loss == "ce" else 1)
     if _compute_dtype(config) == torch.bfloat16:
@@ -247,7 +256,7 @@ def train(config, env, device, rank, world, group: str = "base-demo") -> dict:
     faults = FaultInjector(config.fail_at_iter, config.fail_rank, rank)
     t_start = time.perf_counter()
     engine = config.engine
-    fp8 = _compute_dtype(config) == torch.float8_e4m3fn  # (raises on a width the FP8 path cannot take)
+    fp8 = _compute_dtype(config) in _FP8_DTYPES  # (raises on a width the FP8 / MXFP8 path cannot take)
     if engine == "fused" and (device.type == "cuda" or fp8) and not _fused_supported(config):
         # widths / dtypes the fused step kernel is not instantiated for train through
         # nn.Modules whose Linears run on the MFMA GEMM (FlatDDP + FlatOptimizer)

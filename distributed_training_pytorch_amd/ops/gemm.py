@@ -258,11 +258,19 @@ class MLPFunction(torch.autograd.Function):
     cast once per forward, bf16 activations, fp32 accumulation and fp32 weight /
     bias gradients; fp32 = exact-fp32 MFMA throughout; ``torch.float8_e4m3fn`` = the
     bf16 recipe with every layer whose widths are multiples of 16 on the FP8 GEMM
-    (``ops/fp8.py``: e4m3 activations and weights, e5m2 gradients, per-tensor scales).
+    (``ops/fp8.py``: e4m3 activations and weights, e5m2 gradients, per-tensor scales);
+    ``torch.float8_e8m0fnu`` = the same with every layer whose widths are multiples of 32
+    on the MXFP8 GEMM (``ops/mxfp8.py``: e4m3 throughout, one E8M0 scale per 32 elements).
     """
 
     @staticmethod
     def forward(ctx, x, slope, compute_dtype, *params):
+        ctx.mx = compute_dtype == torch.float8_e8m0fnu
+        if ctx.mx:  # FP8 layer GEMMs with block scales (ops/mxfp8.py)
+            from .mxfp8 import mlp_mxfp8_forward
+
+            ctx.fp8 = False
+            return mlp_mxfp8_forward(ctx, x, slope, params)
         ctx.fp8 = compute_dtype == torch.float8_e4m3fn
         if ctx.fp8:  # FP8 layer GEMMs with per-tensor scales (ops/fp8.py)
             from .fp8 import mlp_fp8_forward
@@ -288,6 +296,10 @@ class MLPFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
+        if ctx.mx:
+            from .mxfp8 import mlp_mxfp8_backward
+
+            return mlp_mxfp8_backward(ctx, gy)
         if ctx.fp8:
             from .fp8 import mlp_fp8_backward
 

@@ -82,7 +82,55 @@ def fp8_layers(widths, batch, rounds, iters):
                               "GB_per_s": round(nbytes / t / 1e6, 1)}), flush=True)
 
 
+def mxfp8_layers(widths, batch, rounds, iters):
+    """--mxfp8: forward / dx / dW of a W-wide Linear at bench_wide.py's batch on the bf16, the
+    per-tensor FP8 and the MXFP8 kernels, interleaved in one process (`rounds` rounds, medians),
+    then both quantisers (both copies): ms and GB/s against x read plus q and qT written."""
+    from distributed_training_pytorch_amd.ops.fp8 import gemm_fp8, quantize_fp8
+    from distributed_training_pytorch_amd.ops.mxfp8 import gemm_mxfp8, quantize_mxfp8
+
+    def rnd(*shape):
+        return torch.rand(*shape, device=DEV) * 2 - 1
+
+    def median(fns):
+        ms = {k: [] for k in fns}
+        for _ in range(rounds):
+            for k, fn in fns.items():
+                ms[k].append(timeit(fn, iters))
+        return {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+
+    for W in widths:
+        h, w, dz = rnd(batch, W).bfloat16(), rnd(W, W), rnd(batch, W).bfloat16()
+        wb = w.bfloat16()
+        hq, wq, dq = (quantize_fp8(h, "e4m3", True), quantize_fp8(w, "e4m3", True), quantize_fp8(dz, "e5m2", True))
+        hm, wm, dm = (quantize_mxfp8(t, "e4m3", True) for t in (h, w, dz))
+        bias, dwf = rnd(W), torch.zeros(W, W, device=DEV)
+        fns = {"fwd": {"bf16": lambda: gemm(h, wb, bias=bias, act=True),
+                       "fp8": lambda: gemm_fp8(hq, wq, bias=bias, act=True),
+                       "mxfp8": lambda: gemm_mxfp8(hm, wm, bias=bias, act=True)},
+               "dx": {"bf16": lambda: gemm(dz, wb, trans_b=True, aux=h),
+                      "fp8": lambda: gemm_fp8(dq, wq, trans_b=True, aux=h),
+                      "mxfp8": lambda: gemm_mxfp8(dm, wm, trans_b=True, aux=h)},
+               "dW": {"bf16": lambda: gemm(dz, h, trans_a=True, trans_b=True, out=dwf, accumulate=True),
+                      "fp8": lambda: gemm_fp8(dq, hq, trans_a=True, trans_b=True, out=dwf, accumulate=True),
+                      "mxfp8": lambda: gemm_mxfp8(dm, hm, trans_a=True, trans_b=True, out=dwf, accumulate=True)}}
+        for name, impls in fns.items():
+            med = median(impls)
+            fl = 2.0 * batch * W * W
+            print(json.dumps({"gemm": name, "W": W, "batch": batch, "rounds": rounds,
+                              **{f"{k}_ms": round(v, 4) for k, v in med.items()},
+                              **{f"{k}_tflops": round(fl / v / 1e9, 1) for k, v in med.items()}}), flush=True)
+    for x in (rnd(8192, 4096).bfloat16(), rnd(4096, 4096)):
+        med = median({"fp8": lambda: quantize_fp8(x, "e4m3", True), "mxfp8": lambda: quantize_mxfp8(x, "e4m3", True)})
+        nbytes = x.numel() * (x.element_size() + 2)
+        print(json.dumps({"quantize": list(x.shape), "in": str(x.dtype), "rounds": rounds,
+                          **{f"{k}_ms": round(v, 4) for k, v in med.items()},
+                          **{f"{k}_GB_per_s": round(nbytes / v / 1e6, 1) for k, v in med.items()}}), flush=True)
+
+
 def main():
+    if "--mxfp8" in sys.argv:
+        return mxfp8_layers((1024, 2048, 4096), 8192, 5, 10)
     if "--fp8" in sys.argv:
         return fp8_layers((1024, 2048, 4096), 8192, 5, 10)
     cases = [(4096, 4096, 4096), (8192, 8192, 8192), (8192, 4096, 4096), (16384, 1024, 1024)]

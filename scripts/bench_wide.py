@@ -37,7 +37,7 @@ def run_ours(a, X, Y, dev, world):
     from distributed_training_pytorch_amd.parallel.ddp import FlatDDP
 
     torch.manual_seed(0)
-    cd = torch.float8_e4m3fn if a.precision == "fp8" else torch.bfloat16
+    cd = {"fp8": torch.float8_e4m3fn, "mxfp8": torch.float8_e8m0fnu}.get(a.precision, torch.bfloat16)
     bank = ModelBank(2, hidden=a.width, depth=a.depth, compute_dtype=cd).to(dev)
     ddp = FlatDDP(bank, flat_params=bank.flat, flat_grad=bank.flat_grad, comm="rccl") if world > 1 else None
     # --shadow: Adam also writes the bf16 weight operands (no per-forward casts). Measured
@@ -100,9 +100,10 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--impl", choices=["ours", "stock", "both"], default="both")
-    ap.add_argument("--precision", choices=["bf16", "fp8"], default="bf16",
+    ap.add_argument("--precision", choices=["bf16", "fp8", "mxfp8"], default="bf16",
                     help="ours: bf16 layer GEMMs, or fp8 (ops/fp8.py: e4m3 x e4m3 forward, e5m2 x e4m3 backward, "
-                         "per-tensor scales; the hidden width must be a multiple of 16)")
+                         "per-tensor scales; the hidden width must be a multiple of 16), or mxfp8 (ops/mxfp8.py: e4m3 "
+                         "throughout, one E8M0 scale per 32 elements; a multiple of 32)")
     ap.add_argument("--shadow", action="store_true",
                     help="ours: the Adam kernel writes the bf16 weight operands (ops/gemm.py ComputeShadow) "
                          "instead of a cast before every forward")
