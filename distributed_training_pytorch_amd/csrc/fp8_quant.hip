@@ -1,6 +1,6 @@
 // Per-tensor scaled FP8 quantiser for gfx950 (CDNA4): OCP e4m3 / e5m2, the operand
-// formats of gemm_fp8.hip.  q = cvt(x * scale), scale = fmax / amax|x| formed and kept on
-// the device (no host read: the pair of launches can sit in a captured graph).
+// formats of gemm_fp8.hip.  q = cvt(x * scale), scale = min(fmax / amax|x|, 2^126) formed and
+// kept on the device (no host read: the pair of launches can sit in a captured graph).
 //
 //  * amax_kernel: at most 1024 workgroups walk x in 16-byte vectors and each writes the
 //    maximum of its |x| bit patterns (an unsigned compare orders non-negative floats) to
@@ -108,7 +108,9 @@ __global__ __launch_bounds__(256) void quantize_kernel(const char* x, long long 
   for (int i = tid; i < nparts; i += 256) mb = max(mb, part[i]);
   const float amax = __uint_as_float(block_max(mb, red, tid));
   constexpr float fmax = FMT == DTP_FP8_E4M3 ? 448.f : 57344.f;
-  const float scale = amax > 0.f ? fmax / amax : 1.f;
+  // capped at 2^126: below amax = fmax / FLT_MAX the quotient is infinite, 1 / scale then 0 and
+  // every output 0 * inf = NaN; with the cap 1 / scale stays a normal number
+  const float scale = amax > 0.f ? fminf(fmax / amax, 0x1p126f) : 1.f;
   if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
     ws[0] = scale;
     ws[1] = 1.f / scale;

@@ -47,9 +47,9 @@
 // Short-K instance (K <= kShortK = 2048): the matrix unit keeps about 15 bits below the largest
 // product of one instruction, scales included, so one loud block costs its quiet neighbours
 // their low bits; a short sum cannot hide that under K 2^-23 of the magnitude sum.  gemm_fp8_short_kernel's plan (64 x 64 tile, 4 waves, no LDS, FP8 bytes decoded
-// to f32 for the exact-fp32 v_mfma_f32_16x16x4_f32) with each decoded value multiplied by its
-// block's power of two, which is exact: the 16 bytes [64 kb + 16 lg, +16) a lane loads are half
-// of MX block 2 kb + (lg >> 1).
+// to f32 for the exact-fp32 v_mfma_f32_16x16x4_f32) with each decoded value multiplied by a power
+// of two from its block's scale (scale_shift() below), which is exact: the 16 bytes [64 kb + 16 lg, +16)
+// a lane loads are half of MX block 2 kb + (lg >> 1).
 #include "gemm_epi.h"
 
 namespace dtp {
@@ -340,8 +340,33 @@ DTP_DEV void decode16(const uint4& g, float mul, float (&f)[16]) {
   }
 }
 
-// 2^(s - 127) of an E8M0 byte (s = 0: the subnormal 2^-127)
-DTP_DEV float e8m0(uint32_t s) { return __uint_as_float(s ? s << 23 : 0x00400000u); }
+// 2^e by v_ldexp_f32: e = -127 (byte 0) gives the subnormal 2^-127, which the fp32 MFMA keeps.
+DTP_DEV float pow2(int e) { return ldexpf(1.f, min(e, 127)); }
+
+// How the two scales of one MX block reach the fp32 MFMA.  Each operand is multiplied by its own
+// 2^(s - 127): exact for every byte the quantiser writes (0 .. 246; 0 .. 239 for e5m2), whatever the
+// other rows of the fragment carry, since s = 0 times the smallest FP8 subnormal is still an fp32
+// subnormal and the largest byte times fmax is still finite.  Only bytes past that range (up to 254,
+// which the format allows and the block-scaled MFMA of the pipelined instance takes) would overflow
+// on their own although the product with a small scale on the other side is an ordinary number.  For
+// those, and only for those, a power of two t moves from one operand to the other: with samax the
+// largest A byte of the wave's 16 rows and sbmax the largest B byte of the tile's 64 rows in this
+// block, t = max(samax - top(A), 0) - max(sbmax - 246, 0), A times 2^(sa - 127 - t), B times
+// 2^(sb - 127 + t).  t is the same for every lane that feeds one k, so each product is unchanged;
+// it is 0 for every quantised tensor, and then this is the plain per-operand scaling.  (Both sides
+// past their range at once: t = 0, the product is past fp32 anyway.)
+template <int FA>
+DTP_DEV int scale_shift(int sa, const int (&sb)[4]) {
+  constexpr int top_a = FA == DTP_FP8_E5M2 ? 239 : 246;  // largest byte with 2^(s - 127) fmax finite
+  int samax = sa, sbmax = max(max(sb[0], sb[1]), max(sb[2], sb[3]));
+#pragma unroll
+  for (int o = 1; o < 16; o <<= 1) {  // over lr: the 16 lanes of one lane group share the block
+    samax = max(samax, __shfl_xor(samax, o, kWave));
+    sbmax = max(sbmax, __shfl_xor(sbmax, o, kWave));
+  }
+  const int ta = max(samax - top_a, 0), tb = max(sbmax - 246, 0);
+  return ta && tb ? 0 : ta - tb;
+}
 
 template <int FA>
 __global__ __launch_bounds__(256) void gemm_mxfp8_short_kernel(DtpGemmMxArgs a) {
@@ -367,12 +392,17 @@ __global__ __launch_bounds__(256) void gemm_mxfp8_short_kernel(DtpGemmMxArgs a) 
     const int k = kb + 16 * lg;
     const bool live = k < a.K;
     const int blk = live ? k >> 5 : 0;  // the MX block these 16 bytes are half of
+    const int sa = sarow[blk];
+    int sb[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sb[j] = sbrow[j][blk];
+    const int sh = scale_shift<FA>(sa, sb);  // (outside any divergence: every lane takes part)
     float fa[16], fb[16];
-    decode16<FA>(live ? *reinterpret_cast<const uint4*>(arow + k) : make_uint4(0, 0, 0, 0), e8m0(sarow[blk]), fa);
+    decode16<FA>(live ? *reinterpret_cast<const uint4*>(arow + k) : make_uint4(0, 0, 0, 0), pow2(sa - 127 - sh), fa);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       decode16<DTP_FP8_E4M3>(live ? *reinterpret_cast<const uint4*>(brow[j] + k) : make_uint4(0, 0, 0, 0),
-                             e8m0(sbrow[j][blk]), fb);
+                             pow2(sb[j] - 127 + sh), fb);
 #pragma unroll
       for (int t = 0; t < 16; ++t) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[t], fb[t], acc[j], 0, 0, 0);
     }

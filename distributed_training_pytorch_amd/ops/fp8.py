@@ -3,9 +3,16 @@
 
 The hybrid recipe: e4m3 for activations and weights, e5m2 for the gradients flowing
 back, fp32 accumulation, one scale per tensor from the tensor's current amax
-(``scale = fmax / amax``, formed and kept on the device: nothing here reads the GPU
-back, so a step can be captured into a hipGraph).  gfx950's formats are the OCP ones,
-``torch.float8_e4m3fn`` and ``torch.float8_e5m2``.
+(``scale = min(fmax / amax, 2^126)``, formed and kept on the device: nothing here reads
+the GPU back, so a step can be captured into a hipGraph).  gfx950's formats are the OCP
+ones, ``torch.float8_e4m3fn`` and ``torch.float8_e5m2``.
+
+The cap: for a tensor whose amax is below ``fmax / FLT_MAX`` (about 1.3e-36 for e4m3,
+1.7e-34 for e5m2: an underflowing gradient) the quotient is infinite, ``1 / scale`` is 0
+and every element, exact zeros included, would come out as ``0 * inf`` = NaN.  With the
+scale capped at 2^126 it is still one correctly rounded division (the kernel and the torch
+definition stay bitwise equal), ``1 / scale`` stays a normal number, zeros stay zeros and
+such a tensor is quantised into the low end of the format instead of poisoning the step.
 
 The GEMM only takes K-contiguous operands, so the quantiser also writes the transposed
 copy when asked (one launch reads ``x`` once and writes both).
@@ -23,6 +30,7 @@ from .. import _native as nat
 from .gemm import _DT, _ld, _ref
 
 _MFMA = 0  # the kernel's matrix instruction: 0 = 16x16x128 f8f6f4, 1 = 16x16x32 fp8 / bf8
+_SCALE_CAP = 2.0 ** 126  # the largest scale (module docstring); fp8_quant.hip holds the same constant
 _FMT = {"e4m3": (torch.float8_e4m3fn, 448.0, nat.FP8_E4M3), "e5m2": (torch.float8_e5m2, 57344.0, nat.FP8_E5M2)}
 
 
@@ -35,7 +43,7 @@ class Fp8Tensor(NamedTuple):
 
 
 def quantize_fp8(x: torch.Tensor, fmt: str = "e4m3", transpose: bool = False) -> Fp8Tensor:
-    """``cvt(x * scale)`` with ``scale = fmax(fmt) / amax|x|`` (1 for an all-zero ``x``), round to
+    """``cvt(x * scale)`` with ``scale = min(fmax(fmt) / amax|x|, 2^126)`` (1 for an all-zero ``x``), round to
     nearest even; ``x`` is [M, K] fp32 or bf16 with K a multiple of 16."""
     if fmt not in _FMT:
         raise ValueError(f"quantize_fp8: fmt {fmt!r} not in {sorted(_FMT)}")
@@ -49,7 +57,7 @@ def quantize_fp8(x: torch.Tensor, fmt: str = "e4m3", transpose: bool = False) ->
         amax = x.detach().abs().max().float()
         # tensor / tensor: one correctly rounded fp32 division, as the kernel's (a python scalar
         # over a tensor is reciprocal-then-multiply, two roundings)
-        scale = torch.where(amax > 0, torch.full_like(amax, fmax) / amax, torch.ones_like(amax))
+        scale = torch.where(amax > 0, (torch.full_like(amax, fmax) / amax).clamp(max=_SCALE_CAP), torch.ones_like(amax))
         q = (x.detach().float() * scale).to(dtype)
         qt = None
         if transpose:

@@ -48,7 +48,7 @@ def test_quantiser_all_zero_input(fmt):
 
 
 # ------------------------------------------------------------------------------ B: GEMM
-def _check_gemm(a, b, M, N, trans, epi):
+def _check_gemm(a, b, M, N, trans, epi, **opt):
     """fp64 product of the dequantised operands; products of two FP8 values are exact in fp32, so
     only the accumulation rounds: |C - ref| <= K U (|A| |B|^T) sa_inv sb_inv, carried through the
     epilogue (every step of it is 1-Lipschitz for slope <= 1), plus one fp32 rounding of the
@@ -74,7 +74,7 @@ def _check_gemm(a, b, M, N, trans, epi):
         ref = lin + old.double()
         mag = mag + old.abs().double()
         kw = dict(out=old.to(DEV), accumulate=True)
-    c = gemm_fp8(a, b, trans_a=trans, trans_b=trans, out_dtype=out_dtype, **kw).double().cpu()
+    c = gemm_fp8(a, b, trans_a=trans, trans_b=trans, out_dtype=out_dtype, **kw, **opt).double().cpu()
     K = A.shape[1]
     tol = K * U * mag + U * mag + (2.0 ** -8 * ref.abs() if out_dtype == torch.bfloat16 else 0.0)
     worst = float(((c - ref).abs() - tol).max())
@@ -118,6 +118,27 @@ def test_gemm_fp8_epilogues(fmt_a, epi, K):
     a = quantize_fp8(_randn(M, K, seed=3).to(DEV), fmt_a)
     b = quantize_fp8(_randn(N, K, seed=4).to(DEV), "e4m3")
     _check_gemm(a, b, M, N, False, epi)
+
+
+# the 16x16x32 fp8 / bf8 MFMAs (mfma=1) in the pipelined kernel, under the same bound
+@pytest.mark.parametrize("fmt_a", ["e4m3", "e5m2"])
+# (the K = 256 row runs on the short instance, which has no MFMA choice: kept so that the option is
+# seen to be ignored there, the 16x16x32 kernels are the K = 272 and 400 rows)
+@pytest.mark.parametrize("MNK", [(80, 64, 256), (272, 264, 272), (272, 264, 400)])
+def test_gemm_fp8_instance_edges_mfma1(fmt_a, MNK):
+    M, N, K = MNK
+    a = quantize_fp8(_randn(M, K, seed=10).to(DEV), fmt_a)
+    b = quantize_fp8(_randn(N, K, seed=11).to(DEV), "e4m3")
+    _check_gemm(a, b, M, N, False, "none", mfma=1)
+
+
+@pytest.mark.parametrize("fmt_a", ["e4m3", "e5m2"])
+@pytest.mark.parametrize("epi", ["none", "bias_act", "aux", "acc"])
+def test_gemm_fp8_epilogues_mfma1(fmt_a, epi):
+    M, N, K = 272, 264, 400
+    a = quantize_fp8(_randn(M, K, seed=3).to(DEV), fmt_a)
+    b = quantize_fp8(_randn(N, K, seed=4).to(DEV), "e4m3")
+    _check_gemm(a, b, M, N, False, epi, mfma=1)
 
 
 def test_gemm_fp8_transposed_copies_with_padded_k():
