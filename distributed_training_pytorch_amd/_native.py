@@ -259,6 +259,9 @@ class GemmFp8Args(ctypes.Structure):
         ("accumulate", c_int),
         ("slope", c_float),
         ("mfma", c_int),
+        ("splitk", c_int),
+        ("work", c_void_p),
+        ("work_bytes", c_longlong),
     ]
 
 
@@ -287,6 +290,9 @@ class GemmMxArgs(ctypes.Structure):
         ("accumulate", c_int),
         ("slope", c_float),
         ("instance", c_int),
+        ("splitk", c_int),
+        ("work", c_void_p),
+        ("work_bytes", c_longlong),
     ]
 
 
@@ -415,9 +421,11 @@ def _declare(lib):
         "dtp_fp8_quantize": (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p,
                                      c_longlong, c_void_p, c_void_p]),
         "dtp_gemm_fp8": (c_int, [P(GemmFp8Args), c_void_p]),
+        "dtp_gemm_fp8_workspace": (c_longlong, [P(GemmFp8Args)]),
         "dtp_mxfp8_quantize": (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p,
                                        c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p]),
         "dtp_gemm_mxfp8": (c_int, [P(GemmMxArgs), c_void_p]),
+        "dtp_gemm_mxfp8_workspace": (c_longlong, [P(GemmMxArgs)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)

@@ -307,9 +307,14 @@ struct DtpGemmFp8Args {
   int accumulate;       // 1: C += result
   float slope;
   int mfma;             // matrix instruction: 0 the 16x16x128 f8f6f4 MFMA, 1 the 16x16x32 fp8 / bf8 MFMAs
+  int splitk;           // K-slices per output tile: 0 the library plans, 1 unsplit, S > 1 forced (tests, probes)
+  void* work;           // split-K partial sums, 4 S M N bytes (uninitialised is fine); unused when unsplit
+  long long work_bytes;
 };
 // C[M,N] (+)= epilogue(sa_inv * sb_inv * A(m,:) . B(n,:)), fp32 accumulation, the epilogues of dtp_gemm
 int dtp_gemm_fp8(const DtpGemmFp8Args* a, void* stream);
+// bytes of DtpGemmFp8Args::work the call would use with splitk = 0 (0: no split-K plan); host only
+long long dtp_gemm_fp8_workspace(const DtpGemmFp8Args* a);
 
 // ---- MXFP8: FP8 with one E8M0 scale byte per 32 elements along K (mxfp8_quant.hip, gemm_mxfp8.hip) ----
 // Block-scaled cast of x [M][ldx] (f32 or bf16, K % 32 == 0, finite).  For each block of 32 along K with
@@ -337,9 +342,13 @@ struct DtpGemmMxArgs {
   int accumulate;            // 1: C += result
   float slope;
   int instance;              // 0: by K; 1: the pipelined block-scaled MFMA kernel; 2: the short-K one (probes)
+  int splitk;                // as DtpGemmFp8Args: 0 planned, 1 unsplit, S > 1 forced (pipelined instance only)
+  void* work;                // 4 S M N bytes
+  long long work_bytes;
 };
 // C[M,N] (+)= epilogue(sum_k A(m,k) 2^(sa(m,k/32)-127) B(n,k) 2^(sb(n,k/32)-127)), fp32 accumulation
 int dtp_gemm_mxfp8(const DtpGemmMxArgs* a, void* stream);
+long long dtp_gemm_mxfp8_workspace(const DtpGemmMxArgs* a);  // as dtp_gemm_fp8_workspace
 
 // sampler probe (tests): dataset indices of steps [t0, t0+n_steps), row-major [n_steps][batch], -1 padded
 int dtp_sampler_indices(const dtp::SamplerCfg* s, long long t0, int n_steps, int* out, void* stream);

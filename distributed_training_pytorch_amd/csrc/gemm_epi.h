@@ -220,5 +220,104 @@ int launch_ph8(const DtpGemmArgs& a, hipStream_t s, int variant);
 int ph8_split_plan(const DtpGemmArgs& a);
 long long ph8_split_bytes(const DtpGemmArgs& a, int splitk);
 
+// ---- split-K of the FP8 / MXFP8 pipelined kernels (gemm_fp8.hip, gemm_mxfp8.hip) ----
+// Slice s of S owns the 128-byte K-tiles [floor(s nk / S), floor((s + 1) nk / S)): uneven
+// slices allowed, none empty while S <= nk.  Each (tile, slice) workgroup stores raw fp32
+// partial sums to work[s][M][N]; f8_splitk_reduce_kernel applies the epilogue.
+struct F8Slice {
+  int t0, nkt;  // first K-tile, K-tiles
+  bool last;    // holds the global last K-tile (the only one that can be ragged)
+};
+// (readfirstlane: the divisions run on the vector unit; the slice bounds are uniform and belong in
+// scalar registers, with the loop count and the DMA base addresses built on them)
+DTP_DEV F8Slice f8_slice(int nk, int splitk, int ks) {
+  ks = __builtin_amdgcn_readfirstlane(ks);
+  const int t0 = __builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<long long>(ks) * nk / splitk));
+  const int t1 = __builtin_amdgcn_readfirstlane(static_cast<int>(static_cast<long long>(ks + 1) * nk / splitk));
+  return F8Slice{t0, t1 - t0, ks == splitk - 1};
+}
+
+// The plan, one rule for both kernels (`pipelined`: the call goes to the 256x256 LDS-DMA
+// instance with the f8f6f4 MFMA).  An fp32 output without activation epilogues and fewer than
+// 128 tiles (the weight gradient of a 1024-2048-wide layer is 16-64 tiles with K = batch): S the
+// largest power of two with tiles * S <= 256 (one workgroup per CU) and at least kF8SplitMinTiles
+// K-tiles in every slice; 0 = no plan.
+// kF8SplitMinTiles: 8 is the shortest slice ph8_split_plan allows (profiles/fp8_gemm/README.md
+// holds the measurement against 4).
+constexpr int kF8SplitMinTiles = 8;
+inline int f8_split_plan(int M, int N, int K, int out_dtype, int act, const void* aux, bool pipelined) {
+  if (!pipelined || out_dtype != DTP_DT_F32 || act || aux) return 0;
+  const long long tiles = (long long)((M + 255) / 256) * ((N + 255) / 256);
+  if (tiles >= 128) return 0;
+  const int nk = (K + 127) / 128;
+  int s = 1;
+  while (tiles * s * 2 <= 256 && nk / (s * 2) >= kF8SplitMinTiles) s *= 2;
+  return s > 1 ? s : 0;
+}
+
+// why a forced splitk = S > 1 cannot run (null: it can)
+inline const char* f8_split_refusal(int M, int N, int K, int out_dtype, int act, const void* aux, bool pipelined,
+                                    int splitk, const void* work, long long work_bytes) {
+  if (splitk < 0) return "splitk must be 0 (planned), 1 (unsplit) or a slice count";
+  if (splitk <= 1) return nullptr;
+  if (out_dtype != DTP_DT_F32 || act || aux) return "split-K needs an fp32 output without act and aux";
+  if (!pipelined) return "split-K runs on the pipelined f8f6f4 instance only (not mfma = 1, not the short-K instance)";
+  if (splitk > (K + 127) / 128) return "more K-slices than 128-byte K-tiles";
+  if (M > 65535) return "split-K: M too large for the reduction grid";
+  if (!work || work_bytes < 4LL * splitk * M * N) return "split-K workspace missing or smaller than 4 S M N bytes";
+  return nullptr;
+}
+
+// C[m][n] = (accumulate ? C : 0) + (alpha * sum_s work[s][m][n] + bias[n]), s ascending, fp32:
+// the expression order of the unsplit epilogue.  SCALED: alpha = *sa_inv * *sb_inv read here
+// (per-tensor FP8: no host read, replays in a hipGraph); otherwise 1 (MXFP8).
+// Block = one output row x 1024 columns, 4 columns per thread: one 16-byte load per slice,
+// contiguous per wave, four slices' loads issued before their adds.  N % 4, ldc % 4 or a C
+// that is only 4-byte aligned (a view at an odd element offset of a flat gradient buffer)
+// take the element path.
+struct F8ReduceArgs {
+  const float* work;  // [splitk][M][N]
+  float* C;           // [M][ldc]
+  const float* bias;  // [N] or null
+  const float* sa_inv;
+  const float* sb_inv;
+  long long ldc;
+  int M, N, splitk, accumulate;
+};
+template <bool SCALED>
+__global__ __launch_bounds__(256) void f8_splitk_reduce_kernel(F8ReduceArgs a) {
+  const int m = blockIdx.y, n = (blockIdx.x * 256 + threadIdx.x) * 4;
+  if (n >= a.N) return;
+  float alpha = 1.f;
+  if constexpr (SCALED) alpha = *a.sa_inv * *a.sb_inv;
+  const long long plane = static_cast<long long>(a.M) * a.N;
+  const float* w = a.work + static_cast<long long>(m) * a.N + n;
+  float* c = a.C + static_cast<long long>(m) * a.ldc + n;
+  const bool vec = a.N % 4 == 0 && a.ldc % 4 == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0;
+  if (vec) {
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    int s = 0;
+    for (; s + 4 <= a.splitk; s += 4) {
+      f32x4 x[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) x[q] = *reinterpret_cast<const f32x4*>(w + (s + q) * plane);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v += x[q];
+    }
+    for (; s < a.splitk; ++s) v += *reinterpret_cast<const f32x4*>(w + s * plane);
+    f32x4* cv = reinterpret_cast<f32x4*>(c);
+    f32x4 o = {0.f, 0.f, 0.f, 0.f}, b = o;
+    if (a.accumulate) o = *cv;
+    if (a.bias) b = f32x4{a.bias[n], a.bias[n + 1], a.bias[n + 2], a.bias[n + 3]};
+    *cv = o + (alpha * v + b);
+  } else {
+    for (int q = 0; q < 4 && n + q < a.N; ++q) {
+      float x = 0.f;
+      for (int s = 0; s < a.splitk; ++s) x += w[s * plane + q];
+      c[q] = (a.accumulate ? c[q] : 0.f) + (alpha * x + (a.bias ? a.bias[n + q] : 0.f));
+    }
+  }
+}
+
 }  // namespace gemm
 }  // namespace dtp

@@ -29,8 +29,16 @@
 //  * ragged M / N: rows clamped on load, guarded on store.  K % 128 != 0: the chunks of the
 //    last K-tile past K are fetched from a 16-byte zero block instead (both operands: a
 //    stray NaN byte times zero would still be NaN).
+//  * split-K (SPLIT instances, dtp_gemm_fp8 with splitk > 1): a weight gradient of a 1024-2048-wide
+//    layer is 16-64 tiles with K = batch, one workgroup per tile leaves most CUs idle.  The grid
+//    becomes tiles x S, each block runs a K-slice (whole K-tiles, possibly uneven) through the
+//    unchanged pipeline and stores raw fp32 partial sums to a workspace; one reduction launch
+//    (f8_splitk_reduce_kernel, gemm_epi.h) sums the slices in order and applies the epilogue.
+//    f8_split_plan picks S.
 //  * K <= 256 does not come here: dtp_gemm_fp8 sends short sums to gemm_fp8_short_kernel (below),
 //    which decodes the same FP8 operands to f32 for the exact-fp32 MFMA.
+#include <string>
+
 #include "gemm_epi.h"
 
 namespace dtp {
@@ -105,48 +113,71 @@ DTP_DEV f32x4 mma_frag(const i32x8& x, const i32x8& y, f32x4 c) {
   }
 }
 
-// FA: format of A (DTP_FP8_*); B is e4m3.  X32: the 16x16x32 MFMAs instead of the 16x16x128 one
-template <int FA, bool X32>
+// FA: format of A (DTP_FP8_*); B is e4m3.  X32: the 16x16x32 MFMAs instead of the 16x16x128 one.
+// SPLIT: grid = tiles x a.splitk, neighbouring blocks are one tile's K-slices (f8_slice: they share
+// the operand rows in L2 and differ in K offset); the block runs its slice's K-tiles through the
+// same pipeline and stores raw fp32 partial sums to a.work[ks][M][N] (plain stores: the workspace
+// is uninitialised and no atomic target); f8_splitk_reduce_kernel applies the epilogue.
+template <int FA, bool X32, bool SPLIT>
 __global__ __launch_bounds__(kThreads) void gemm_fp8_kernel(DtpGemmFp8Args a) {
+  static_assert(!(X32 && SPLIT), "the 16x16x32 instance has no split twin");
   __shared__ __align__(16) char lds[kLds];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
 
   DtpGemmArgs e{};  // the epilogue's view of the problem (gemm_epi.h)
-  e.C = a.C;
-  e.bias = a.bias;
-  e.aux = a.aux;
-  e.ldc = a.ldc;
-  e.ldaux = a.ldaux;
   e.M = a.M;
   e.N = a.N;
   e.K = a.K;
   e.dtype = DTP_DT_BF16;
-  e.out_dtype = a.out_dtype;
-  e.act = a.act;
-  e.accumulate = a.accumulate;
-  e.splitk = 1;
-  e.slope = a.slope;
-  e.alpha = *a.sa_inv * *a.sb_inv;
+  if constexpr (SPLIT) {  // raw partial sums: no bias, aux, act or accumulate, alpha = 1
+    e.ldc = a.N;
+    e.out_dtype = DTP_DT_F32;
+    e.splitk = a.splitk;  // (for decode_tile; 1 again before the stores)
+    e.alpha = 1.f;
+  } else {
+    e.C = a.C;
+    e.bias = a.bias;
+    e.aux = a.aux;
+    e.ldc = a.ldc;
+    e.ldaux = a.ldaux;
+    e.out_dtype = a.out_dtype;
+    e.act = a.act;
+    e.accumulate = a.accumulate;
+    e.splitk = 1;
+    e.slope = a.slope;
+    e.alpha = *a.sa_inv * *a.sb_inv;
+  }
 
   const TileId id = decode_tile<256, 256>(e);
   const int m0 = id.m0, n0 = id.n0;
-  const int nk = (a.K + 127) >> 7;  // K-tiles
-  const int ktail = a.K & 127;      // valid bytes of the last K-tile (0: all 128)
+  const int ktail = a.K & 127;  // valid bytes of the last K-tile (0: all 128)
+  // this block's K-tiles: nk of them from tile kt0 on; the global last K-tile, the only ragged one,
+  // is its tile ktl (>= nk: in another slice)
+  int nk = (a.K + 127) >> 7, kt0 = 0;
+  int ktl = nk - 1;
+  if constexpr (SPLIT) {
+    const F8Slice sl = f8_slice(nk, a.splitk, id.ks);
+    nk = sl.nkt;
+    kt0 = sl.t0;
+    ktl -= sl.t0;
+    e.C = static_cast<float*>(a.work) + static_cast<long long>(id.ks) * a.M * a.N;
+    e.splitk = 1;
+  }
 
   uint32_t oSA[2][2], oSB[2][2];
   part_sources(oSA, a.lda, m0, a.M, wave, lane);
   part_sources(oSB, a.ldb, n0, a.N, wave, lane);
-  const char* gA = static_cast<const char*>(a.A) + m0 * a.lda;
-  const char* gB = static_cast<const char*>(a.B) + n0 * a.ldb;
+  const char* gA = static_cast<const char*>(a.A) + m0 * a.lda + static_cast<uint32_t>(kt0) * 128u;
+  const char* gB = static_cast<const char*>(a.B) + n0 * a.ldb + static_cast<uint32_t>(kt0) * 128u;
   // the source chunk of this lane in every DMA instruction (fswz reads row bits 0, 1, 3 =
   // lane bits 3, 4 and wave bit 0: the same for both instructions and both parts)
   const int csrc = (lane & 7) ^ fswz((wave * 8 + (lane >> 3)) & 15);
   const bool dead = ktail && csrc * 16 >= ktail;
   const char* zero = reinterpret_cast<const char*>(&g_zero_chunk);
 
-  // one part (P: 0 = A0, 1 = A1, 2 = B0, 3 = B1) of K-tile `tile` into its buffer, or into
-  // the sink past the last tile (same wait accounting every phase)
+  // one part (P: 0 = A0, 1 = A1, 2 = B0, 3 = B1) of K-tile `tile` (counted from the block's
+  // first) into its buffer, or into the sink past the last tile (same wait accounting every phase)
   auto stage = [&](auto P, int tile) {
     constexpr int p = decltype(P)::value;
     const bool real = tile < nk;
@@ -155,7 +186,8 @@ __global__ __launch_bounds__(kThreads) void gemm_fp8_kernel(DtpGemmFp8Args a) {
     const char* g = (p < 2 ? gA : gB) + static_cast<uint32_t>(real ? tile : 0) * 128u;
     const uint32_t* o = p < 2 ? oSA[p & 1] : oSB[p & 1];
     // the ragged K-tile (a sink slot re-reads tile 0): chunks past K come from the zero block
-    const bool cut = dead && (real ? tile == nk - 1 : nk == 1);
+    // (the unsplit instances keep their own form of the same test: ktl = nk - 1 there)
+    const bool cut = dead && (SPLIT ? (real ? tile : 0) == ktl : (real ? tile == nk - 1 : nk == 1));
 #pragma unroll
     for (int i = 0; i < 2; ++i)
       __builtin_amdgcn_global_load_lds((gbl_void_t*)(cut ? zero : g + o[i]), (lds_void_t*)(dst + i * 8192), 16, 0, 0);
@@ -362,10 +394,19 @@ __global__ __launch_bounds__(256) void gemm_fp8_short_kernel(DtpGemmFp8Args a) {
 }  // namespace gemm
 }  // namespace dtp
 
+// the call goes to the pipelined kernel's f8f6f4 instance: the one with a split twin
+static bool fp8_splittable(const DtpGemmFp8Args& a) { return a.K > dtp::gemm::f8::kShortK && a.mfma != 1; }
+
+extern "C" long long dtp_gemm_fp8_workspace(const DtpGemmFp8Args* in) {
+  if (!in || in->splitk != 0 || in->M <= 0 || in->N <= 0 || in->K <= 0) return 0;
+  const int sp = dtp::gemm::f8_split_plan(in->M, in->N, in->K, in->out_dtype, in->act, in->aux, fp8_splittable(*in));
+  return sp > 1 ? 4LL * sp * in->M * in->N : 0;
+}
+
 extern "C" int dtp_gemm_fp8(const DtpGemmFp8Args* in, void* stream) {
   using namespace dtp;
   if (!in) return set_err(1, "dtp_gemm_fp8: null args");
-  const DtpGemmFp8Args& a = *in;
+  DtpGemmFp8Args a = *in;
   if (a.M <= 0 || a.N <= 0 || a.K <= 0) return set_err(1, "dtp_gemm_fp8: empty problem");
   if (!a.A || !a.B || !a.C || !a.sa_inv || !a.sb_inv) return set_err(1, "dtp_gemm_fp8: null operand or scale");
   if (a.fmt_b != DTP_FP8_E4M3 || (a.fmt_a != DTP_FP8_E4M3 && a.fmt_a != DTP_FP8_E5M2))
@@ -377,6 +418,13 @@ extern "C" int dtp_gemm_fp8(const DtpGemmFp8Args* in, void* stream) {
   if (a.ldc < a.N || (a.aux && a.ldaux < a.N)) return set_err(1, "dtp_gemm_fp8: C / aux rows shorter than N");
   const long long two_gib = 1LL << 31;
   if (a.M * a.lda >= two_gib || a.N * a.ldb >= two_gib) return set_err(1, "dtp_gemm_fp8: operands must be under 2 GiB");
+  if (a.splitk == 0) {  // the plan, if the caller brought its workspace
+    const int sp = gemm::f8_split_plan(a.M, a.N, a.K, a.out_dtype, a.act, a.aux, fp8_splittable(a));
+    a.splitk = (sp > 1 && a.M <= 65535 && a.work && a.work_bytes >= 4LL * sp * a.M * a.N) ? sp : 1;
+  }
+  if (const char* why = gemm::f8_split_refusal(a.M, a.N, a.K, a.out_dtype, a.act, a.aux, fp8_splittable(a), a.splitk,
+                                               a.work, a.work_bytes))
+    return set_err(-1, (std::string("dtp_gemm_fp8: ") + why).c_str());
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (a.K <= gemm::f8::kShortK) {  // short sums: the exact-fp32 instance (see gemm_fp8_short_kernel)
     const dim3 gs((a.N + 63) / 64, (a.M + 63) / 64), bs(256);
@@ -386,12 +434,23 @@ extern "C" int dtp_gemm_fp8(const DtpGemmFp8Args* in, void* stream) {
     return check_launch("dtp_gemm_fp8(short K)");
   }
   const long long tiles = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-  const dim3 g((unsigned)tiles), b(gemm::f8::kThreads);
+  const dim3 b(gemm::f8::kThreads);
+  if (a.splitk > 1) {  // tiles x S workgroups of partial sums, then the reduction with the epilogue
+    const dim3 g((unsigned)(tiles * a.splitk));
+    if (a.fmt_a == DTP_FP8_E4M3) hipLaunchKernelGGL((gemm::f8::gemm_fp8_kernel<DTP_FP8_E4M3, false, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((gemm::f8::gemm_fp8_kernel<DTP_FP8_E5M2, false, true>), g, b, 0, s, a);
+    if (int err = check_launch("dtp_gemm_fp8(256x256x128, split-K)")) return err;
+    const gemm::F8ReduceArgs r{static_cast<const float*>(a.work), static_cast<float*>(a.C), a.bias, a.sa_inv, a.sb_inv,
+                               a.ldc, a.M, a.N, a.splitk, a.accumulate};
+    hipLaunchKernelGGL(gemm::f8_splitk_reduce_kernel<true>, dim3((a.N + 1023) / 1024, a.M), dim3(256), 0, s, r);
+    return check_launch("dtp_gemm_fp8(split-K reduction)");
+  }
+  const dim3 g((unsigned)tiles);
   switch ((a.fmt_a == DTP_FP8_E5M2 ? 2 : 0) | (a.mfma == 1 ? 1 : 0)) {
-    case 0: hipLaunchKernelGGL((gemm::f8::gemm_fp8_kernel<DTP_FP8_E4M3, false>), g, b, 0, s, a); break;
-    case 1: hipLaunchKernelGGL((gemm::f8::gemm_fp8_kernel<DTP_FP8_E4M3, true>), g, b, 0, s, a); break;
-    case 2: hipLaunchKernelGGL((gemm::f8::gemm_fp8_kernel<DTP_FP8_E5M2, false>), g, b, 0, s, a); break;
-    default: hipLaunchKernelGGL((gemm::f8::gemm_fp8_kernel<DTP_FP8_E5M2, true>), g, b, 0, s, a); break;
+    case 0: hipLaunchKernelGGL((gemm::f8::gemm_fp8_kernel<DTP_FP8_E4M3, false, false>), g, b, 0, s, a); break;
+    case 1: hipLaunchKernelGGL((gemm::f8::gemm_fp8_kernel<DTP_FP8_E4M3, true, false>), g, b, 0, s, a); break;
+    case 2: hipLaunchKernelGGL((gemm::f8::gemm_fp8_kernel<DTP_FP8_E5M2, false, false>), g, b, 0, s, a); break;
+    default: hipLaunchKernelGGL((gemm::f8::gemm_fp8_kernel<DTP_FP8_E5M2, true, false>), g, b, 0, s, a); break;
   }
   return check_launch("dtp_gemm_fp8(256x256x128)");
 }

@@ -40,6 +40,11 @@
 //    prologue (5 parts issued, B0 and A0 of tile 0 retired) as in every phase.  The scale
 //    bytes are read under the same barrier / lgkmcnt(0) discipline as the fragments, so the
 //    buffer-reuse (WAR) argument of the operand parts covers them unchanged.
+//  * split-K (SPLIT instances, splitk > 1): as gemm_fp8.hip -- grid tiles x S, each block one K-slice
+//    of whole K-tiles, raw fp32 partial sums to a workspace, f8_splitk_reduce_kernel for the
+//    epilogue.  A slice's scale DMA starts 4 bytes per K-tile of its offset into the same rows.
+//    Splitting changes neither the set of matrix instructions nor their products, only which
+//    workgroup issues them: the short-K rule stays a function of the whole K.
 //  * K % 128 != 0: the dead chunks of the last K-tile come from a zero block, as in gemm_fp8.hip;
 //    their scale bytes are the 127s the quantiser wrote.  Rows past M / N are clamped on load
 //    (data and scales), guarded on store.
@@ -50,6 +55,8 @@
 // to f32 for the exact-fp32 v_mfma_f32_16x16x4_f32) with each decoded value multiplied by a power
 // of two from its block's scale (scale_shift() below), which is exact: the 16 bytes [64 kb + 16 lg, +16)
 // a lane loads are half of MX block 2 kb + (lg >> 1).
+#include <string>
+
 #include "gemm_epi.h"
 
 namespace dtp {
@@ -141,40 +148,65 @@ DTP_DEV DtpGemmArgs epi_args(const DtpGemmMxArgs& a) {
   return e;
 }
 
-// FA: format of A (DTP_FP8_*); B is e4m3
-template <int FA>
+// FA: format of A (DTP_FP8_*); B is e4m3.  SPLIT: grid = tiles x a.splitk, the block runs K-slice
+// id.ks (f8_slice) and stores raw fp32 partial sums to a.work[ks][M][N]
+template <int FA, bool SPLIT>
 __global__ __launch_bounds__(kThreads) void gemm_mxfp8_kernel(DtpGemmMxArgs a) {
   __shared__ __align__(16) char lds[kLds];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 2, wc = wave & 3;
-  const DtpGemmArgs e = epi_args(a);
+  DtpGemmArgs e{};
+  if constexpr (SPLIT) {  // raw partial sums: no bias, aux, act or accumulate, alpha = 1
+    e.M = a.M;
+    e.N = a.N;
+    e.K = a.K;
+    e.dtype = DTP_DT_BF16;
+    e.ldc = a.N;
+    e.out_dtype = DTP_DT_F32;
+    e.splitk = a.splitk;  // (for decode_tile; 1 again before the stores)
+    e.alpha = 1.f;
+  } else {
+    e = epi_args(a);
+  }
 
   const TileId id = decode_tile<256, 256>(e);
   const int m0 = id.m0, n0 = id.n0;
-  const int nk = (a.K + 127) >> 7;  // K-tiles
-  const int ktail = a.K & 127;      // valid bytes of the last K-tile (0: all 128)
+  const int ktail = a.K & 127;  // valid bytes of the last K-tile (0: all 128)
+  // this block's K-tiles: nk of them from tile kt0 on; the global last K-tile, the only ragged one,
+  // is its tile ktl (>= nk: in another slice)
+  int nk = (a.K + 127) >> 7, kt0 = 0;
+  int ktl = nk - 1;
+  if constexpr (SPLIT) {
+    const F8Slice sl = f8_slice(nk, a.splitk, id.ks);
+    nk = sl.nkt;
+    kt0 = sl.t0;
+    ktl -= sl.t0;
+    e.C = static_cast<float*>(a.work) + static_cast<long long>(id.ks) * a.M * a.N;
+    e.splitk = 1;
+  }
 
   uint32_t oSA[2][2], oSB[2][2];
   part_sources(oSA, a.lda, m0, a.M, wave, lane);
   part_sources(oSB, a.ldb, n0, a.N, wave, lane);
-  const char* gA = static_cast<const char*>(a.A) + m0 * a.lda;
-  const char* gB = static_cast<const char*>(a.B) + n0 * a.ldb;
+  const char* gA = static_cast<const char*>(a.A) + m0 * a.lda + static_cast<uint32_t>(kt0) * 128u;
+  const char* gB = static_cast<const char*>(a.B) + n0 * a.ldb + static_cast<uint32_t>(kt0) * 128u;
   // the source chunk of this lane in every DMA instruction (fswz reads row bits 0, 1, 3 =
   // lane bits 3, 4 and wave bit 0: the same for both instructions and both parts)
   const int csrc = (lane & 7) ^ fswz((wave * 8 + (lane >> 3)) & 15);
   const bool dead = ktail && csrc * 16 >= ktail;
-  // scale rows of this lane in the scale DMA of parts A0, A1, B0, B1 (clamped as the operand rows)
+  // scale rows of this lane in the scale DMA of parts A0, A1, B0, B1 (clamped as the operand rows),
+  // at the dword of the block's first K-tile
   uint32_t oSS[4];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int r = 128 * i + (wave & 1) * 64 + lane;
-    oSS[i] = static_cast<uint32_t>(min(m0 + r, a.M - 1)) * static_cast<uint32_t>(a.ldsa);
-    oSS[2 + i] = static_cast<uint32_t>(min(n0 + r, a.N - 1)) * static_cast<uint32_t>(a.ldsb);
+    oSS[i] = static_cast<uint32_t>(min(m0 + r, a.M - 1)) * static_cast<uint32_t>(a.ldsa) + kt0 * 4u;
+    oSS[2 + i] = static_cast<uint32_t>(min(n0 + r, a.N - 1)) * static_cast<uint32_t>(a.ldsb) + kt0 * 4u;
   }
   const char* zero = reinterpret_cast<const char*>(&g_zero_chunk);
 
-  // one part (P: 0 = A0, 1 = A1, 2 = B0, 3 = B1) of K-tile `tile` into its buffer, or into
-  // the sink past the last tile (same wait accounting every phase)
+  // one part (P: 0 = A0, 1 = A1, 2 = B0, 3 = B1) of K-tile `tile` (counted from the block's
+  // first) into its buffer, or into the sink past the last tile (same wait accounting every phase)
   auto stage = [&](auto P, int tile) {
     constexpr int p = decltype(P)::value;
     const bool real = tile < nk;
@@ -183,7 +215,8 @@ __global__ __launch_bounds__(kThreads) void gemm_mxfp8_kernel(DtpGemmMxArgs a) {
     const char* g = (p < 2 ? gA : gB) + static_cast<uint32_t>(real ? tile : 0) * 128u;
     const uint32_t* o = p < 2 ? oSA[p & 1] : oSB[p & 1];
     // the ragged K-tile (a sink slot re-reads tile 0): chunks past K come from the zero block
-    const bool cut = dead && (real ? tile == nk - 1 : nk == 1);
+    // (the unsplit instances keep their own form of the same test: ktl = nk - 1 there)
+    const bool cut = dead && (SPLIT ? (real ? tile : 0) == ktl : (real ? tile == nk - 1 : nk == 1));
 #pragma unroll
     for (int i = 0; i < 2; ++i)
       __builtin_amdgcn_global_load_lds((gbl_void_t*)(cut ? zero : g + o[i]), (lds_void_t*)(dst + i * 8192), 16, 0, 0);
@@ -426,10 +459,21 @@ __global__ __launch_bounds__(256) void gemm_mxfp8_short_kernel(DtpGemmMxArgs a) 
 }  // namespace gemm
 }  // namespace dtp
 
+// the call goes to the pipelined instance: the one with a split twin
+static bool mx_pipelined(const DtpGemmMxArgs& a) {
+  return !(a.instance == 2 || (a.instance != 1 && a.K <= dtp::gemm::mx::kShortK));
+}
+
+extern "C" long long dtp_gemm_mxfp8_workspace(const DtpGemmMxArgs* in) {
+  if (!in || in->splitk != 0 || in->M <= 0 || in->N <= 0 || in->K <= 0) return 0;
+  const int sp = dtp::gemm::f8_split_plan(in->M, in->N, in->K, in->out_dtype, in->act, in->aux, mx_pipelined(*in));
+  return sp > 1 ? 4LL * sp * in->M * in->N : 0;
+}
+
 extern "C" int dtp_gemm_mxfp8(const DtpGemmMxArgs* in, void* stream) {
   using namespace dtp;
   if (!in) return set_err(1, "dtp_gemm_mxfp8: null args");
-  const DtpGemmMxArgs& a = *in;
+  DtpGemmMxArgs a = *in;
   if (a.M <= 0 || a.N <= 0 || a.K <= 0) return set_err(1, "dtp_gemm_mxfp8: empty problem");
   if (!a.A || !a.B || !a.C || !a.sa || !a.sb) return set_err(1, "dtp_gemm_mxfp8: null operand or scale");
   if (a.fmt_b != DTP_FP8_E4M3 || (a.fmt_a != DTP_FP8_E4M3 && a.fmt_a != DTP_FP8_E5M2))
@@ -446,8 +490,15 @@ extern "C" int dtp_gemm_mxfp8(const DtpGemmMxArgs* in, void* stream) {
   const long long two_gib = 1LL << 31;
   if (a.M * a.lda >= two_gib || a.N * a.ldb >= two_gib || a.M * a.ldsa >= two_gib || a.N * a.ldsb >= two_gib)
     return set_err(1, "dtp_gemm_mxfp8: operands must be under 2 GiB");
+  const bool short_k = !mx_pipelined(a);
+  if (a.splitk == 0) {  // the plan, if the caller brought its workspace
+    const int sp = gemm::f8_split_plan(a.M, a.N, a.K, a.out_dtype, a.act, a.aux, !short_k);
+    a.splitk = (sp > 1 && a.M <= 65535 && a.work && a.work_bytes >= 4LL * sp * a.M * a.N) ? sp : 1;
+  }
+  if (const char* why = gemm::f8_split_refusal(a.M, a.N, a.K, a.out_dtype, a.act, a.aux, !short_k, a.splitk, a.work,
+                                               a.work_bytes))
+    return set_err(-1, (std::string("dtp_gemm_mxfp8: ") + why).c_str());
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool short_k = a.instance == 2 || (a.instance != 1 && a.K <= gemm::mx::kShortK);
   if (short_k) {  // short sums: the exact-fp32 instance (see gemm_mxfp8_short_kernel)
     const dim3 gs((a.N + 63) / 64, (a.M + 63) / 64), bs(256);
     if (gs.y > 65535) return set_err(1, "dtp_gemm_mxfp8: M too large for the short-K instance");
@@ -456,8 +507,19 @@ extern "C" int dtp_gemm_mxfp8(const DtpGemmMxArgs* in, void* stream) {
     return check_launch("dtp_gemm_mxfp8(short K)");
   }
   const long long tiles = (long long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-  const dim3 g((unsigned)tiles), b(gemm::mx::kThreads);
-  if (a.fmt_a == DTP_FP8_E4M3) hipLaunchKernelGGL((gemm::mx::gemm_mxfp8_kernel<DTP_FP8_E4M3>), g, b, 0, s, a);
-  else hipLaunchKernelGGL((gemm::mx::gemm_mxfp8_kernel<DTP_FP8_E5M2>), g, b, 0, s, a);
+  const dim3 b(gemm::mx::kThreads);
+  if (a.splitk > 1) {  // tiles x S workgroups of partial sums, then the reduction with the epilogue
+    const dim3 g((unsigned)(tiles * a.splitk));
+    if (a.fmt_a == DTP_FP8_E4M3) hipLaunchKernelGGL((gemm::mx::gemm_mxfp8_kernel<DTP_FP8_E4M3, true>), g, b, 0, s, a);
+    else hipLaunchKernelGGL((gemm::mx::gemm_mxfp8_kernel<DTP_FP8_E5M2, true>), g, b, 0, s, a);
+    if (int err = check_launch("dtp_gemm_mxfp8(256x256x128, split-K)")) return err;
+    const gemm::F8ReduceArgs r{static_cast<const float*>(a.work), static_cast<float*>(a.C), a.bias, nullptr, nullptr,
+                               a.ldc, a.M, a.N, a.splitk, a.accumulate};
+    hipLaunchKernelGGL(gemm::f8_splitk_reduce_kernel<false>, dim3((a.N + 1023) / 1024, a.M), dim3(256), 0, s, r);
+    return check_launch("dtp_gemm_mxfp8(split-K reduction)");
+  }
+  const dim3 g((unsigned)tiles);
+  if (a.fmt_a == DTP_FP8_E4M3) hipLaunchKernelGGL((gemm::mx::gemm_mxfp8_kernel<DTP_FP8_E4M3, false>), g, b, 0, s, a);
+  else hipLaunchKernelGGL((gemm::mx::gemm_mxfp8_kernel<DTP_FP8_E5M2, false>), g, b, 0, s, a);
   return check_launch("dtp_gemm_mxfp8(256x256x128)");
 }

@@ -30,6 +30,7 @@ from .. import _native as nat
 from .gemm import _DT, _ld, _ref
 
 _MFMA = 0  # the kernel's matrix instruction: 0 = 16x16x128 f8f6f4, 1 = 16x16x32 fp8 / bf8
+_SHORT_K = 256  # gemm_fp8.hip's kShortK: sums up to here run on the exact-fp32 short-K instance
 _SCALE_CAP = 2.0 ** 126  # the largest scale (module docstring); fp8_quant.hip holds the same constant
 _FMT = {"e4m3": (torch.float8_e4m3fn, 448.0, nat.FP8_E4M3), "e5m2": (torch.float8_e5m2, 57344.0, nat.FP8_E5M2)}
 
@@ -84,15 +85,52 @@ def _operand(t: Fp8Tensor, trans: bool, name: str) -> torch.Tensor:
     return d
 
 
+def check_split_k(who: str, split_k: int | None, K: int, out_dtype: torch.dtype, act: bool, aux, pipelined: bool,
+                  why_not: str) -> None:
+    """A forced ``split_k``: S >= 1, and S > 1 only where the split-K instances run (an fp32 output without
+    ``act`` / ``aux`` on the pipelined f8f6f4 kernel, at most one slice per 128-byte K-tile)."""
+    if split_k is None:
+        return
+    if not isinstance(split_k, int) or split_k < 1:
+        raise ValueError(f"{who}: split_k must be None (planned) or an int >= 1, got {split_k!r}")
+    if split_k == 1:
+        return
+    if out_dtype != torch.float32 or act or aux is not None:
+        raise ValueError(f"{who}: split_k > 1 needs an fp32 output without act and aux")
+    if not pipelined:
+        raise ValueError(f"{who}: split_k > 1 runs on the pipelined 16x16x128 kernel only ({why_not})")
+    if split_k > -(-K // 128):
+        raise ValueError(f"{who}: split_k = {split_k} exceeds the {-(-K // 128)} 128-byte K-tiles of K = {K}")
+
+
+def split_workspace(args, query, split_k: int | None, device) -> torch.Tensor | None:
+    """Set ``args.splitk`` / ``work`` / ``work_bytes``: the library's plan (``query``: its workspace size, 0 = no
+    plan) for ``None``, a forced slice count otherwise.  The workspace comes from torch's caching allocator
+    (stream-ordered, capturable); the caller keeps the returned tensor until the launch is queued."""
+    if split_k is None and (args.out_dtype != nat.DT_F32 or args.act or args.aux):
+        args.splitk = 1  # no plan for these (forward / dx): spare them the query
+        return None
+    args.splitk = 0 if split_k is None else split_k
+    nbytes = query(args) if split_k is None else (4 * split_k * args.M * args.N if split_k > 1 else 0)
+    if not nbytes:
+        return None
+    work = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    args.work, args.work_bytes = nat.ptr(work), nbytes
+    return work
+
+
 def gemm_fp8(a: Fp8Tensor, b: Fp8Tensor, *, trans_a: bool = False, trans_b: bool = False,
              bias: torch.Tensor | None = None, aux: torch.Tensor | None = None, act: bool = False, slope: float = 0.01,
              out: torch.Tensor | None = None, accumulate: bool = False,
-             out_dtype: torch.dtype | None = None, mfma: int = _MFMA) -> torch.Tensor:
+             out_dtype: torch.dtype | None = None, mfma: int = _MFMA, split_k: int | None = None) -> torch.Tensor:
     """C[M,N] (+)= epilogue(a.scale_inv * b.scale_inv * A(m,k) B(n,k)), fp32 accumulation.
 
     A is ``a.data`` [M,K] (``a.data_t`` with ``trans_a``), B is ``b.data`` [N,K] (``b.data_t`` with
     ``trans_b``): e4m3 x e4m3 or e5m2 x e4m3.  Epilogue order as ``gemm``: + bias[n],
-    * LeakyReLU'(aux[m,n]) (aux bf16), LeakyReLU, (+ old C), cast to bf16 or fp32."""
+    * LeakyReLU'(aux[m,n]) (aux bf16), LeakyReLU, (+ old C), cast to bf16 or fp32.
+    ``split_k``: K-slices per output tile.  ``None``: the library plans (a few-tile fp32 problem with a
+    long K, the weight gradient of a 1024-2048-wide layer, is split over the idle CUs); 1: unsplit;
+    S > 1: forced (tests and probes).  The sum is the same; on CPU tensors it is only checked."""
     A, B = _operand(a, trans_a, "a"), _operand(b, trans_b, "b")
     (M, K), (N, Kb) = A.shape, B.shape
     if K != Kb:
@@ -108,6 +146,9 @@ def gemm_fp8(a: Fp8Tensor, b: Fp8Tensor, *, trans_a: bool = False, trans_b: bool
         raise ValueError(f"gemm_fp8: out must be [{M},{N}] {out_dtype}")
     if aux is not None and (aux.shape != (M, N) or aux.dtype != torch.bfloat16):
         raise ValueError("gemm_fp8: aux must be a bf16 [M,N]")
+    Kp = -(-K // 16) * 16  # a transposed copy's rows are padded with zeros to 16 bytes: the kernel sums over the padded K
+    check_split_k("gemm_fp8", split_k, Kp, out_dtype, act, aux, Kp > _SHORT_K and int(mfma) != 1,
+                  f"not mfma = 1, not K <= {_SHORT_K}")
     if A.device.type != "cuda" or not nat.native_enabled():
         r = _ref(A.float(), B.float(), False, False, bias, aux, act, slope, a.scale_inv * b.scale_inv)
         if accumulate:
@@ -117,8 +158,6 @@ def gemm_fp8(a: Fp8Tensor, b: Fp8Tensor, *, trans_a: bool = False, trans_b: bool
     lib = nat.require(A.device)
     if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
         bias = bias.float().contiguous()
-    # a transposed copy's rows are padded with zeros to 16 bytes: the kernel sums over the padded K
-    Kp = -(-K // 16) * 16
     if Kp != K and not (trans_a and trans_b):
         raise ValueError(f"gemm_fp8: K = {K} is not a multiple of 16 (only two transposed copies carry the padding)")
     args = nat.GemmFp8Args()
@@ -132,6 +171,7 @@ def gemm_fp8(a: Fp8Tensor, b: Fp8Tensor, *, trans_a: bool = False, trans_b: bool
     args.out_dtype = _DT[out_dtype]
     args.act, args.accumulate, args.slope = int(act), int(accumulate), float(slope)
     args.mfma = int(mfma)
+    work = split_workspace(args, lib.dtp_gemm_fp8_workspace, split_k, A.device)  # noqa: F841 (alive until queued)
     nat.check(lib.dtp_gemm_fp8(args, nat.stream_ptr()), "dtp_gemm_fp8")
     return out
 

@@ -27,10 +27,12 @@ from typing import NamedTuple
 import torch
 
 from .. import _native as nat
+from .fp8 import check_split_k, split_workspace
 from .gemm import _DT, _ld, _ref
 
 _FMT = {"e4m3": (torch.float8_e4m3fn, 448.0, 8, nat.FP8_E4M3), "e5m2": (torch.float8_e5m2, 57344.0, 15, nat.FP8_E5M2)}
 BLOCK = 32
+_SHORT_K = 2048  # gemm_mxfp8.hip's kShortK: by default sums up to here run on the exact-fp32 short-K instance
 
 
 class MxTensor(NamedTuple):
@@ -111,13 +113,14 @@ def _operand(t: MxTensor, trans: bool, who: str, name: str):
 def gemm_mxfp8(a: MxTensor, b: MxTensor, *, trans_a: bool = False, trans_b: bool = False,
                bias: torch.Tensor | None = None, aux: torch.Tensor | None = None, act: bool = False,
                slope: float = 0.01, out: torch.Tensor | None = None, accumulate: bool = False,
-               out_dtype: torch.dtype | None = None, instance: int = 0) -> torch.Tensor:
+               out_dtype: torch.dtype | None = None, instance: int = 0, split_k: int | None = None) -> torch.Tensor:
     """C[M,N] (+)= epilogue(sum_k A(m,k) 2^(sa(m,k/32)-127) B(n,k) 2^(sb(n,k/32)-127)), fp32 accumulation.
 
     A is ``a.data`` [M,K] (``a.data_t`` with ``trans_a``), B is ``b.data`` [N,K] (``b.data_t`` with
     ``trans_b``), each with its scale array: e4m3 x e4m3 or e5m2 x e4m3.  Epilogue order as ``gemm``:
     + bias[n], * LeakyReLU'(aux[m,n]) (aux bf16), LeakyReLU, (+ old C), cast to bf16 or fp32.
-    ``instance``: 0 = by K, 1 = the pipelined block-scaled MFMA kernel, 2 = the short-K one (probes)."""
+    ``instance``: 0 = by K, 1 = the pipelined block-scaled MFMA kernel, 2 = the short-K one (probes).
+    ``split_k``: as ``gemm_fp8`` (``None`` planned, 1 unsplit, S > 1 forced; the pipelined instance only)."""
     (A, SA), (B, SB) = _operand(a, trans_a, "gemm_mxfp8", "a"), _operand(b, trans_b, "gemm_mxfp8", "b")
     (M, K), (N, Kb) = A.shape, B.shape
     if K != Kb:
@@ -135,6 +138,8 @@ def gemm_mxfp8(a: MxTensor, b: MxTensor, *, trans_a: bool = False, trans_b: bool
         raise ValueError(f"gemm_mxfp8: out must be [{M},{N}] {out_dtype}")
     if aux is not None and (aux.shape != (M, N) or aux.dtype != torch.bfloat16):
         raise ValueError("gemm_mxfp8: aux must be a bf16 [M,N]")
+    check_split_k("gemm_mxfp8", split_k, K, out_dtype, act, aux, instance == 1 or (instance != 2 and K > _SHORT_K),
+                  f"instance = 1 or K > {_SHORT_K}")
     if A.device.type != "cuda" or not nat.native_enabled():
         r = _ref(dequantize_mxfp8(a, trans_a, torch.float32), dequantize_mxfp8(b, trans_b, torch.float32), False, False,
                  bias, aux, act, slope, 1.0)
@@ -157,6 +162,7 @@ def gemm_mxfp8(a: MxTensor, b: MxTensor, *, trans_a: bool = False, trans_b: bool
     args.out_dtype = _DT[out_dtype]
     args.act, args.accumulate, args.slope = int(act), int(accumulate), float(slope)
     args.instance = int(instance)
+    work = split_workspace(args, lib.dtp_gemm_mxfp8_workspace, split_k, A.device)  # noqa: F841 (alive until queued)
     nat.check(lib.dtp_gemm_mxfp8(args, nat.stream_ptr()), "dtp_gemm_mxfp8")
     return out
 

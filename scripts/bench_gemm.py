@@ -65,6 +65,9 @@ def fp8_layers(widths, batch, rounds, iters):
             fns["fwd"][tag] = lambda m=m: gemm_fp8(hq, wq, bias=bias, act=True, mfma=m)
             fns["dx"][tag] = lambda m=m: gemm_fp8(dq, wq, trans_b=True, aux=h, mfma=m)
             fns["dW"][tag] = lambda m=m: gemm_fp8(dq, hq, trans_a=True, trans_b=True, out=dwf, accumulate=True, mfma=m)
+        # the planned split-K dW (fp8_x128, where a plan exists) next to the same GEMM unsplit
+        fns["dW"]["fp8_x128_unsplit"] = lambda: gemm_fp8(dq, hq, trans_a=True, trans_b=True, out=dwf, accumulate=True,
+                                                         split_k=1)
         for name, impls in fns.items():
             ms = {k: [] for k in impls}
             for _ in range(rounds):
@@ -113,7 +116,12 @@ def mxfp8_layers(widths, batch, rounds, iters):
                       "mxfp8": lambda: gemm_mxfp8(dm, wm, trans_b=True, aux=h)},
                "dW": {"bf16": lambda: gemm(dz, h, trans_a=True, trans_b=True, out=dwf, accumulate=True),
                       "fp8": lambda: gemm_fp8(dq, hq, trans_a=True, trans_b=True, out=dwf, accumulate=True),
-                      "mxfp8": lambda: gemm_mxfp8(dm, hm, trans_a=True, trans_b=True, out=dwf, accumulate=True)}}
+                      "mxfp8": lambda: gemm_mxfp8(dm, hm, trans_a=True, trans_b=True, out=dwf, accumulate=True),
+                      # the planned split-K dW (above, where a plan exists) next to the same GEMMs unsplit
+                      "fp8_unsplit": lambda: gemm_fp8(dq, hq, trans_a=True, trans_b=True, out=dwf, accumulate=True,
+                                                      split_k=1),
+                      "mxfp8_unsplit": lambda: gemm_mxfp8(dm, hm, trans_a=True, trans_b=True, out=dwf, accumulate=True,
+                                                          split_k=1)}}
         for name, impls in fns.items():
             med = median(impls)
             fl = 2.0 * batch * W * W
