@@ -69,12 +69,16 @@ def build_parser(description: str | None = None) -> argparse.ArgumentParser:
                    help="each rank draws its own dataset (the reference's unseeded behaviour)")
     p.add_argument("--hidden", type=int, default=10)
     p.add_argument("--depth", type=int, default=3, help="number of hidden Linear(h,h) layers")
-    p.add_argument("--precision", choices=["fp32", "bf16", "fp8", "mxfp8"], default="fp32",
+    p.add_argument("--fp8_amax_history", type=int, default=16,
+                   help="--precision fp8-delayed: amaxes kept per tensor; its scale is fmax over their maximum (1..1024)")
+    p.add_argument("--precision", choices=["fp32", "bf16", "fp8", "fp8-delayed", "mxfp8"], default="fp32",
                    help="fp32 = the reference (precision=32); bf16 = bf16 matmul operands with fp32 "
                         "accumulation, fp32 master weights and optimizer (fused toy kernels have bf16 "
                         "instances; wide models run bf16 on the MFMA GEMM path); fp8 = the bf16 recipe with the "
                         "hidden Linears on the FP8 GEMM (e4m3 activations and weights, e5m2 gradients, per-tensor "
-                        "scales): module engine only, --hidden a multiple of 16; mxfp8 = the same with block "
+                        "scales): module engine only, --hidden a multiple of 16; fp8-delayed = fp8 with each scale "
+                        "taken from the tensor's amax history (--fp8_amax_history), so the GEMM epilogues emit the "
+                        "next layer's FP8 operand and no tensor is read back to be quantised; mxfp8 = fp8 with block "
                         "scales (OCP MX: e4m3 throughout, one power-of-two scale per 32 elements): module engine "
                         "only, --hidden a multiple of 32")
     p.add_argument("--timeout_min", type=float, default=60.0, help="process-group timeout (demo.py:27)")

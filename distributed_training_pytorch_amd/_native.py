@@ -265,6 +265,32 @@ class GemmFp8Args(ctypes.Structure):
     ]
 
 
+class Fp8QuantOut(ctypes.Structure):  # DtpFp8QuantOut
+    _fields_ = [
+        ("q", c_void_p),
+        ("qT", c_void_p),
+        ("scale", c_void_p),
+        ("part", c_void_p),
+        ("ldq", c_longlong),
+        ("ldqt", c_longlong),
+        ("fmt", c_int),
+        ("cap", c_int),
+    ]
+
+
+class Fp8ScaleRec(ctypes.Structure):  # DtpFp8ScaleRec
+    _fields_ = [
+        ("partials", c_void_p),
+        ("history", c_void_p),
+        ("scale", c_void_p),
+        ("pos", c_void_p),
+        ("cap", c_int),
+        ("H", c_int),
+        ("fmax", c_float),
+        ("pad_", c_int),
+    ]
+
+
 class GemmMxArgs(ctypes.Structure):
     _fields_ = [
         ("A", c_void_p),
@@ -420,7 +446,12 @@ def _declare(lib):
         "dtp_colsum": (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
         "dtp_fp8_quantize": (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p,
                                      c_longlong, c_void_p, c_void_p]),
+        "dtp_fp8_amax": (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+        "dtp_fp8_quantize_scaled": (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_longlong,
+                                            c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_void_p]),
+        "dtp_fp8_scale_update": (c_int, [c_void_p, c_int, c_void_p]),
         "dtp_gemm_fp8": (c_int, [P(GemmFp8Args), c_void_p]),
+        "dtp_gemm_fp8_quant": (c_int, [P(GemmFp8Args), P(Fp8QuantOut), c_void_p]),
         "dtp_gemm_fp8_workspace": (c_longlong, [P(GemmFp8Args)]),
         "dtp_mxfp8_quantize": (c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_int, c_void_p, c_longlong, c_void_p,
                                        c_longlong, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p]),

@@ -291,6 +291,29 @@ int dtp_colsum(const void* X, long long ld, int M, int N, int dtype, float* out,
 int dtp_fp8_quantize(const void* x, long long ldx, int M, int K, int dtype, int fmt, void* q, long long ldq,
                      void* qT, long long ldt, float* ws, void* stream);
 
+// -- delayed scaling: the scale comes from the amaxes of earlier steps, so it is known before the tensor is --
+// One record per quantised tensor.  `partials`: word 0 the count n of partials its last producer wrote
+// (0: nothing since the last update), words 1 .. n the maxima of |x| as f32 bit patterns; every producer
+// (dtp_fp8_amax, dtp_fp8_quantize_scaled, dtp_gemm_fp8 with q) overwrites all of its n words and the count.
+struct DtpFp8ScaleRec {
+  unsigned* partials;  // [1 + cap]
+  float* history;      // [H] ring of amaxes, zeros while empty
+  float* scale;        // [2]: scale, 1 / scale
+  int* pos;            // next ring slot
+  int cap, H;          // H <= 1024
+  float fmax;          // 448 (e4m3) or 57344 (e5m2)
+  int pad_;
+};
+// For each record: n > 0: push max(partials) into the ring and set the count to 0; then
+// scale = min(fmax / max(history), 2^126), 1 if that maximum is 0, and 1 / scale.  One launch, no host read.
+int dtp_fp8_scale_update(DtpFp8ScaleRec* recs, int n_recs, void* stream);
+// amax partials of x (as dtp_fp8_quantize's first launch) into the record layout: part[0] = n, part[1 .. n]
+int dtp_fp8_amax(const void* x, long long ldx, int M, int K, int dtype, unsigned* part, int cap, void* stream);
+// dtp_fp8_quantize with a given scale: q = cvt_rne(clamp(x * *scale, -fmax, fmax)); one launch reads x once,
+// writes q, qT (may be null) and the amax partials of x (one per 64 x 64 tile; cap >= tiles).
+int dtp_fp8_quantize_scaled(const void* x, long long ldx, int M, int K, int dtype, int fmt, void* q, long long ldq,
+                            void* qT, long long ldt, const float* scale, unsigned* part, int cap, void* stream);
+
 struct DtpGemmFp8Args {
   const void* A;        // [M][lda] fp8 (fmt_a), K-contiguous
   const void* B;        // [N][ldb] fp8 (fmt_b), K-contiguous
@@ -313,6 +336,23 @@ struct DtpGemmFp8Args {
 };
 // C[M,N] (+)= epilogue(sa_inv * sb_inv * A(m,:) . B(n,:)), fp32 accumulation, the epilogues of dtp_gemm
 int dtp_gemm_fp8(const DtpGemmFp8Args* a, void* stream);
+// Quantised output for delayed scaling.  Needs a bf16 C without accumulate or split-K, and N % 16 == 0:
+// q[m*ldq+n] = cvt_rne(clamp(C_bf16[m][n] * *scale, -fmax, fmax)) in format fmt, qT[n*ldqt+m] likewise
+// (qT may be null; ldqt >= M rounded up to 16, columns [M, that) written as zeros), and part receives
+// the |C_bf16| amax partials in the layout of DtpFp8ScaleRec::partials (cap >= 8 per 256 x 256 tile).
+struct DtpFp8QuantOut {
+  void* q;
+  void* qT;
+  const float* scale;  // device scalar
+  unsigned* part;
+  long long ldq, ldqt;
+  int fmt;             // DTP_FP8_*
+  int cap;
+};
+// dtp_gemm_fp8 that also emits C quantised: the pipelined kernel's epilogue writes q, qT and part itself;
+// the short-K instance and an unaligned C / aux run the plain GEMM and then dtp_fp8_quantize_scaled on C:
+// the same bits either way.  qo null: dtp_gemm_fp8.
+int dtp_gemm_fp8_quant(const DtpGemmFp8Args* a, const DtpFp8QuantOut* qo, void* stream);
 // bytes of DtpGemmFp8Args::work the call would use with splitk = 0 (0: no split-K plan); host only
 long long dtp_gemm_fp8_workspace(const DtpGemmFp8Args* a);
 

@@ -92,11 +92,11 @@ _FP8_DTYPES = (torch.float8_e4m3fn, torch.float8_e8m0fnu)
 
 def _compute_dtype(config) -> torch.dtype:
     precision = getattr(config, "precision", "fp32")
-    if precision == "fp8":
+    if precision in ("fp8", "fp8-delayed"):
         if config.hidden % 16:
             # the FP8 GEMM reads 16-byte operand rows; a narrower hidden width would leave every
             # layer on the bf16 kernels, which is not what the flag asks for
-            raise ValueError(f"--precision fp8 needs --hidden to be a multiple of 16 (got {config.hidden}): a Linear "
+            raise ValueError(f"--precision {precision} needs --hidden to be a multiple of 16 (got {config.hidden}): a Linear "
                              "runs on the FP8 GEMM only if both its widths are multiples of 16")
         return torch.float8_e4m3fn
     if precision == "mxfp8":
@@ -106,6 +106,13 @@ def _compute_dtype(config) -> torch.dtype:
                              "runs on the MXFP8 GEMM only if both its widths are multiples of 32")
         return torch.float8_e8m0fnu
     return torch.bfloat16 if precision == "bf16" else torch.float32
+
+
+def _fp8_recipe(config) -> dict:
+    """ModelBank keywords of the FP8 scaling recipe: --precision fp8-delayed = scales from an amax history."""
+    if getattr(config, "precision", "fp32") != "fp8-delayed":
+        return {}
+    return {"fp8_recipe": "delayed", "fp8_amax_history": int(getattr(config, "fp8_amax_history", 16))}
 
 
 def _fused_supported(config) -> bool:
@@ -292,6 +299,9 @@ def train(config, env, device, rank, world, group: str = "base-demo") -> dict:
     summary["optimizer"] = "adam" if summary.get("engine") == "stock" and config.optimizer != "adamw" \
         else _optim(config).label
     summary.update(_lr_summary(config, int(summary.get("iters", 0))))
+    if fp8 and _compute_dtype(config) == torch.float8_e4m3fn:  # the per-tensor scaling recipe that ran
+        r = _fp8_recipe(config)
+        summary["fp8_recipe"] = f"delayed (amax history {r['fp8_amax_history']})" if r else "current"
     rank_print(rank, "Finished")
     return summary
 
@@ -420,7 +430,7 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
     torch.manual_seed(config.seed)
     out_f = 4 if config.loss == "ce" else 1
     bank = ModelBank(2, hidden=config.hidden, depth=config.depth, out_features=out_f,
-                     compute_dtype=_compute_dtype(config)).to(device)
+                     compute_dtype=_compute_dtype(config), **_fp8_recipe(config)).to(device)
     ddp = FlatDDP(bank, flat_params=bank.flat, flat_grad=bank.flat_grad,
                   comm=config.comm if config.comm in ("auto", "rccl", "xgmi") else "rccl")
     rank_print(rank, f"engine: module (FlatDDP over {ddp.comm})")
@@ -446,6 +456,8 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
             opt.load_state_dict(st["optim_state"])
             start = int(st["iteration"])
             rank_print(rank, f"resumed from {config.checkpoint_dir} at iteration {start}")
+            if _fp8_recipe(config):  # amax histories are not in checkpoints
+                rank_print(rank, "fp8-delayed: amax histories are not checkpointed; the first step re-seeds every scale")
 
     def _save(it_done):
         checkpoint.save({"engine": "module", "params": bank.flat.detach(), "optim_state": opt.state_dict(),

@@ -26,10 +26,14 @@ from ..ops.mlp import MlpSpec, fused_mlp
 
 class ToyModel(nn.Module):
     def __init__(self, in_features: int = 2, hidden: int = 10, depth: int = 3, out_features: int = 1,
-                 slope: float = 0.01, compute_dtype: torch.dtype = torch.float32):
+                 slope: float = 0.01, compute_dtype: torch.dtype = torch.float32, fp8_recipe: str = "current",
+                 fp8_amax_history: int = 16):
         super().__init__()
         self.spec = MlpSpec(in_features, hidden, depth + 2, out_features, False, slope)
         self.compute_dtype = compute_dtype
+        if fp8_recipe not in ("current", "delayed"):
+            raise ValueError(f"fp8_recipe must be 'current' or 'delayed', got {fp8_recipe!r}")
+        self.fp8_recipe, self.fp8_amax_history = fp8_recipe, int(fp8_amax_history)
         self._fused: bool | None = None
         mods: list[nn.Module] = [nn.Linear(in_features, hidden), nn.LeakyReLU(slope)]
         for _ in range(depth):
@@ -86,6 +90,18 @@ class ToyModel(nn.Module):
                 p.copy_(flat[o:o + p.numel()].view_as(p).to(p))
                 o += p.numel()
 
+    def _fp8_state(self, weights):
+        """The delayed-scaling state (``fp8_recipe='delayed'``), made on the first forward on the weights' device;
+        a fresh one (re-seeded on its first step) after the module moved."""
+        if self.fp8_recipe != "delayed" or self.compute_dtype != torch.float8_e4m3fn:
+            return None
+        st = getattr(self, "_fp8", None)
+        if st is None or st.device != weights[0].device:
+            from ..ops.fp8 import delayed_state_for
+
+            st = self._fp8 = delayed_state_for(weights, self.fp8_amax_history)
+        return st
+
     def uses_fused_kernel(self) -> bool:
         if self._fused is None:
             self._fused = self.compute_dtype == torch.float32 and self.spec.native_supported()
@@ -118,5 +134,7 @@ class ToyModel(nn.Module):
                 return fused_mlp(x.float(), self.spec, list(self.layers.parameters()), bf16=True)
             lin = [m for m in self.layers if isinstance(m, nn.Linear)]
             with torch.autocast("cuda", enabled=False):
-                return gemm_mlp(x, [m.weight for m in lin], [m.bias for m in lin], self.spec.slope, cd)
+                ws = [m.weight for m in lin]
+                return gemm_mlp(x, ws, [m.bias for m in lin], self.spec.slope, cd,
+                                fp8_state=self._fp8_state(ws) if cd == self.compute_dtype else None)
         return self.layers(x)

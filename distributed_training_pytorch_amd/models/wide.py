@@ -18,8 +18,11 @@ from ..ops.gemm import mlp
 
 class WideMLP(nn.Module):
     def __init__(self, widths=(2, 1024, 1024, 1024, 1024, 1), slope: float = 0.01,
-                 compute_dtype: torch.dtype = torch.float32):
+                 compute_dtype: torch.dtype = torch.float32, fp8_recipe: str = "current", fp8_amax_history: int = 16):
         super().__init__()
+        if fp8_recipe not in ("current", "delayed"):
+            raise ValueError(f"fp8_recipe must be 'current' or 'delayed', got {fp8_recipe!r}")
+        self.fp8_recipe, self.fp8_amax_history = fp8_recipe, int(fp8_amax_history)
         if len(widths) < 2:
             raise ValueError("WideMLP needs at least an input and an output width")
         self.widths = tuple(int(w) for w in widths)
@@ -53,12 +56,25 @@ class WideMLP(nn.Module):
         self._flatten()
         return out
 
+    def _fp8_state(self, weights):
+        """The delayed-scaling state (``fp8_recipe='delayed'``), made on the first forward on the weights' device;
+        a fresh one (re-seeded on its first step) after the module moved."""
+        if self.fp8_recipe != "delayed" or self.compute_dtype != torch.float8_e4m3fn:
+            return None
+        st = getattr(self, "_fp8", None)
+        if st is None or st.device != weights[0].device:
+            from ..ops.fp8 import delayed_state_for
+
+            st = self._fp8 = delayed_state_for(weights, self.fp8_amax_history)
+        return st
+
     def linears(self) -> list[nn.Linear]:
         return [m for m in self.layers if isinstance(m, nn.Linear)]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         lin = self.linears()
-        return mlp(x, [m.weight for m in lin], [m.bias for m in lin], self.slope, self.compute_dtype)
+        ws = [m.weight for m in lin]
+        return mlp(x, ws, [m.bias for m in lin], self.slope, self.compute_dtype, fp8_state=self._fp8_state(ws))
 
     def reference_forward(self, x: torch.Tensor) -> torch.Tensor:
         """Plain PyTorch forward of the same module tree (tests / stock baseline)."""

@@ -43,14 +43,173 @@ class Fp8Tensor(NamedTuple):
     fmt: str
 
 
-def quantize_fp8(x: torch.Tensor, fmt: str = "e4m3", transpose: bool = False) -> Fp8Tensor:
+_PART_CAP = 16384  # amax partials per tensor of a delayed-scaling state (one per 64 x 64 tile, or 8 per GEMM tile)
+
+
+class Fp8Slot(NamedTuple):
+    """One tensor of an ``Fp8DelayedState``: what ``quantize_fp8(scale=...)`` and ``gemm_fp8(quant_out=...)`` take."""
+    state: "Fp8DelayedState"
+    index: int
+
+
+class Fp8DelayedState:
+    """Delayed scaling for ``n_tensors`` quantised tensors: per tensor a ring of the last ``history`` amaxes,
+    the scale ``min(fmax / max(ring), 2^126)`` (1 while the ring holds only zeros) with its inverse, and the
+    amax partials that the tensor's last producer wrote (word 0 their count).  ``update()`` is one launch
+    over all of them (``csrc/fp8_quant.hip`` scale_update_kernel): each tensor whose producer ran since the
+    last update has its amax pushed into its ring, and every scale is formed again.  Everything lives on the
+    device; nothing is read back, so a step replays in a hipGraph once every tensor it touches is seeded.
+
+    Seeding: the first time a tensor is quantised, its scale comes from its own amax (amax launch, update of
+    that one record, given-scale quantiser): current scaling built from the same pieces.  That path cannot
+    be captured into a graph (it depends on host state) and raises if tried."""
+
+    def __init__(self, n_tensors: int, history: int = 16, device="cpu"):
+        if n_tensors < 1 or not 1 <= int(history) <= 1024:
+            raise ValueError(f"Fp8DelayedState: n_tensors >= 1 and 1 <= history <= 1024, got {n_tensors}, {history}")
+        self.n, self.H, self.device = int(n_tensors), int(history), torch.device(device)
+        dev = self.device
+        self.history = torch.zeros(self.n, self.H, dtype=torch.float32, device=dev)
+        self.scales = torch.ones(self.n, 2, dtype=torch.float32, device=dev)  # scale, 1 / scale
+        self.partials = torch.zeros(self.n, 1 + _PART_CAP, dtype=torch.int32, device=dev)
+        self.pos = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        self.seeded = [False] * self.n
+        self.fmt: list[str | None] = [None] * self.n
+        self._recs = None
+        if dev.type == "cuda" and nat.native_enabled():
+            self._write_records()
+
+    def _write_records(self) -> None:
+        import ctypes
+
+        recs = (nat.Fp8ScaleRec * self.n)()
+        for i, r in enumerate(recs):
+            r.partials, r.history = nat.ptr(self.partials[i]), nat.ptr(self.history[i])
+            r.scale, r.pos = nat.ptr(self.scales[i]), nat.ptr(self.pos[i:i + 1])
+            r.cap, r.H, r.fmax = _PART_CAP, self.H, _FMT[self.fmt[i] or "e4m3"][1]
+        host = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8)
+        if self._recs is None:
+            self._recs = torch.empty(ctypes.sizeof(recs), dtype=torch.uint8, device=self.device)
+        self._recs.copy_(host)
+        self._rec_bytes = ctypes.sizeof(nat.Fp8ScaleRec)
+
+    def slot(self, index: int) -> Fp8Slot:
+        if not 0 <= index < self.n:
+            raise IndexError(f"Fp8DelayedState: slot {index} of {self.n}")
+        return Fp8Slot(self, index)
+
+    def bind(self, index: int, fmt: str) -> None:
+        """The format of tensor ``index`` (its fmax goes into the record); fixed at first use."""
+        if self.fmt[index] == fmt:
+            return
+        if self.fmt[index] is not None:
+            raise ValueError(f"Fp8DelayedState: slot {index} holds {self.fmt[index]} tensors, not {fmt}")
+        if torch.cuda.is_available() and self.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("Fp8DelayedState: a tensor's first use cannot be captured into a graph; run a step eagerly first")
+        self.fmt[index] = fmt
+        if self._recs is not None:
+            self._write_records()
+
+    def set_scale(self, index: int, scale, fmt: str = "e4m3") -> None:
+        """Give tensor ``index`` a scale by hand (tests, probes); it counts as seeded."""
+        self.bind(index, fmt)
+        s = torch.as_tensor(scale, dtype=torch.float32, device=self.device)
+        self.scales[index, 0] = s
+        self.scales[index, 1] = torch.ones_like(s) / s
+        self.seeded[index] = True
+
+    def amax_of(self, index: int) -> torch.Tensor:
+        """The maximum of the tensor's current partials (0 if its producer has not run since the last update)."""
+        p = self.partials[index]
+        live = torch.arange(_PART_CAP, device=p.device) < p[0]
+        return torch.where(live, p[1:], torch.zeros_like(p[1:])).max().view(torch.float32)
+
+    def update(self, index: int | None = None) -> None:
+        """Push and rescale every tensor (``index``: that one only).  One launch; no host read."""
+        if self._recs is not None:
+            lib = nat.require(self.device)
+            first, count = (0, self.n) if index is None else (index, 1)
+            nat.check(lib.dtp_fp8_scale_update(nat.ptr(self._recs) + first * self._rec_bytes, count, nat.stream_ptr()),
+                      "dtp_fp8_scale_update")
+            return
+        for i in (range(self.n) if index is None else (index,)):  # the torch definition of the same math
+            if int(self.partials[i, 0]) > 0:
+                p = int(self.pos[i])
+                self.history[i, p] = self.amax_of(i)
+                self.pos[i] = (p + 1) % self.H
+                self.partials[i, 0] = 0
+            amax = self.history[i].abs().max()
+            fmax = torch.full_like(amax, _FMT[self.fmt[i] or "e4m3"][1])
+            scale = torch.where(amax > 0, (fmax / amax).clamp(max=_SCALE_CAP), torch.ones_like(amax))
+            self.scales[i, 0] = scale
+            self.scales[i, 1] = torch.ones_like(scale) / scale
+
+
+def fp8_amax(x: torch.Tensor, slot: Fp8Slot) -> None:
+    """The amax partials of ``x`` into the slot's record (``dtp_fp8_amax``, the first launch of the
+    current-scaling quantiser on its own): what seeds a delayed scale."""
+    st, i = slot
+    M, K = x.shape
+    if x.device.type != "cuda" or not nat.native_enabled():
+        st.partials[i, 1] = x.detach().float().abs().max().view(torch.int32)
+        st.partials[i, 0] = 1
+        return
+    lib = nat.require(x.device)
+    nat.check(lib.dtp_fp8_amax(nat.ptr(x), _ld(x, "x"), M, K, _DT[x.dtype], nat.ptr(st.partials[i]), _PART_CAP,
+                               nat.stream_ptr()), "dtp_fp8_amax")
+
+
+def _quantize_given(x: torch.Tensor, fmt: str, transpose: bool, slot: Fp8Slot) -> Fp8Tensor:
+    """``cvt(clamp(x * scale, -fmax, fmax))`` with the slot's scale; the slot's partials receive amax|x|."""
+    st, i = slot
+    dtype, fmax, code = _FMT[fmt]
+    st.bind(i, fmt)
+    x = x.detach()
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    if not st.seeded[i]:  # current scaling from the same pieces: amax, the one record's update, then below
+        if x.device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("quantize_fp8: an unseeded Fp8DelayedState cannot be captured into a graph; run a step "
+                               "eagerly first")
+        fp8_amax(x, slot)
+        st.update(i)
+        st.seeded[i] = True
+    M, K = x.shape
+    Mp = -(-M // 16) * 16
+    scale, scale_inv = st.scales[i, 0], st.scales[i, 1]
+    if x.device.type != "cuda" or not nat.native_enabled():
+        q = (x.float() * scale).clamp(-fmax, fmax).to(dtype)
+        qt = None
+        if transpose:
+            qt = torch.zeros(K, Mp, dtype=dtype)
+            qt[:, :M] = q.t()
+            qt = qt[:, :M]
+        st.partials[i, 1] = x.float().abs().max().view(torch.int32)
+        st.partials[i, 0] = 1
+        return Fp8Tensor(q, qt, scale, scale_inv, fmt)
+    lib = nat.require(x.device)
+    q = torch.empty(M, K, dtype=dtype, device=x.device)
+    qt = torch.empty(K, Mp, dtype=dtype, device=x.device) if transpose else None
+    nat.check(lib.dtp_fp8_quantize_scaled(nat.ptr(x), _ld(x, "x"), M, K, _DT[x.dtype], code, nat.ptr(q), K, nat.ptr(qt), Mp,
+                                          nat.ptr(scale), nat.ptr(st.partials[i]), _PART_CAP, nat.stream_ptr()),
+              "dtp_fp8_quantize_scaled")
+    return Fp8Tensor(q, None if qt is None else qt[:, :M], scale, scale_inv, fmt)
+
+
+def quantize_fp8(x: torch.Tensor, fmt: str = "e4m3", transpose: bool = False, scale: Fp8Slot | None = None) -> Fp8Tensor:
     """``cvt(x * scale)`` with ``scale = min(fmax(fmt) / amax|x|, 2^126)`` (1 for an all-zero ``x``), round to
-    nearest even; ``x`` is [M, K] fp32 or bf16 with K a multiple of 16."""
+    nearest even; ``x`` is [M, K] fp32 or bf16 with K a multiple of 16.
+
+    ``scale``: a slot of an ``Fp8DelayedState``.  The scale is then the slot's (from earlier steps' amaxes),
+    ``x * scale`` is clamped to +-fmax before the convert (a stale scale saturates), and the one launch that
+    reads ``x`` also leaves amax|x| in the slot for the next ``update()``."""
     if fmt not in _FMT:
         raise ValueError(f"quantize_fp8: fmt {fmt!r} not in {sorted(_FMT)}")
     if x.dim() != 2 or x.dtype not in _DT or x.shape[1] % 16 or 0 in x.shape:
         raise ValueError(f"quantize_fp8: x must be a non-empty fp32 / bf16 [M, K] with K a multiple of 16, got "
                          f"{x.dtype} {tuple(x.shape)}")
+    if scale is not None:
+        return _quantize_given(x, fmt, transpose, scale)
     dtype, fmax, code = _FMT[fmt]
     M, K = x.shape
     Mp = -(-M // 16) * 16
@@ -122,8 +281,16 @@ def split_workspace(args, query, split_k: int | None, device) -> torch.Tensor | 
 def gemm_fp8(a: Fp8Tensor, b: Fp8Tensor, *, trans_a: bool = False, trans_b: bool = False,
              bias: torch.Tensor | None = None, aux: torch.Tensor | None = None, act: bool = False, slope: float = 0.01,
              out: torch.Tensor | None = None, accumulate: bool = False,
-             out_dtype: torch.dtype | None = None, mfma: int = _MFMA, split_k: int | None = None) -> torch.Tensor:
+             out_dtype: torch.dtype | None = None, mfma: int = _MFMA, split_k: int | None = None,
+             quant_out: tuple[str, Fp8Slot] | None = None):
     """C[M,N] (+)= epilogue(a.scale_inv * b.scale_inv * A(m,k) B(n,k)), fp32 accumulation.
+
+    ``quant_out = (fmt, slot)``: also return C quantised with the slot's delayed scale, row-major and
+    transposed, as ``(C, Fp8Tensor)``: ``q = cvt(clamp(C * scale, -fmax, fmax))`` of the bf16 C, bit for bit
+    what ``quantize_fp8(C, fmt, True, scale=slot)`` gives; amax|C| goes to the slot.  On the pipelined
+    kernel its epilogue writes all of it (no quantiser launch, C is not read back); short K, unaligned
+    views and an unseeded slot run the GEMM and the quantiser one after the other.  Needs a bf16 C,
+    no ``accumulate`` and N a multiple of 16.
 
     A is ``a.data`` [M,K] (``a.data_t`` with ``trans_a``), B is ``b.data`` [N,K] (``b.data_t`` with
     ``trans_b``): e4m3 x e4m3 or e5m2 x e4m3.  Epilogue order as ``gemm``: + bias[n],
@@ -149,6 +316,16 @@ def gemm_fp8(a: Fp8Tensor, b: Fp8Tensor, *, trans_a: bool = False, trans_b: bool
     Kp = -(-K // 16) * 16  # a transposed copy's rows are padded with zeros to 16 bytes: the kernel sums over the padded K
     check_split_k("gemm_fp8", split_k, Kp, out_dtype, act, aux, Kp > _SHORT_K and int(mfma) != 1,
                   f"not mfma = 1, not K <= {_SHORT_K}")
+    if quant_out is not None:
+        qfmt, slot = quant_out
+        if qfmt not in _FMT or out_dtype != torch.bfloat16 or accumulate or N % 16 or split_k not in (None, 1):
+            raise ValueError("gemm_fp8: quant_out needs fmt e4m3 / e5m2, a bf16 out without accumulate or split_k, "
+                             f"and N a multiple of 16 (got {qfmt!r}, {out_dtype}, N = {N})")
+        slot.state.bind(slot.index, qfmt)
+        if A.device.type != "cuda" or not nat.native_enabled() or not slot.state.seeded[slot.index]:
+            c = gemm_fp8(a, b, trans_a=trans_a, trans_b=trans_b, bias=bias, aux=aux, act=act, slope=slope, out=out,
+                         out_dtype=out_dtype, mfma=mfma)
+            return c, quantize_fp8(c, qfmt, True, scale=slot)
     if A.device.type != "cuda" or not nat.native_enabled():
         r = _ref(A.float(), B.float(), False, False, bias, aux, act, slope, a.scale_inv * b.scale_inv)
         if accumulate:
@@ -172,8 +349,18 @@ def gemm_fp8(a: Fp8Tensor, b: Fp8Tensor, *, trans_a: bool = False, trans_b: bool
     args.act, args.accumulate, args.slope = int(act), int(accumulate), float(slope)
     args.mfma = int(mfma)
     work = split_workspace(args, lib.dtp_gemm_fp8_workspace, split_k, A.device)  # noqa: F841 (alive until queued)
-    nat.check(lib.dtp_gemm_fp8(args, nat.stream_ptr()), "dtp_gemm_fp8")
-    return out
+    if quant_out is None:
+        nat.check(lib.dtp_gemm_fp8(args, nat.stream_ptr()), "dtp_gemm_fp8")
+        return out
+    st, i = slot
+    Mp = -(-M // 16) * 16
+    q = torch.empty(M, N, dtype=_FMT[qfmt][0], device=A.device)
+    qt = torch.empty(N, Mp, dtype=_FMT[qfmt][0], device=A.device)
+    qo = nat.Fp8QuantOut()
+    qo.q, qo.qT, qo.ldq, qo.ldqt = nat.ptr(q), nat.ptr(qt), N, Mp
+    qo.scale, qo.part, qo.cap, qo.fmt = nat.ptr(st.scales[i, 0]), nat.ptr(st.partials[i]), _PART_CAP, _FMT[qfmt][2]
+    nat.check(lib.dtp_gemm_fp8_quant(args, qo, nat.stream_ptr()), "dtp_gemm_fp8_quant")
+    return out, Fp8Tensor(q, qt[:, :M], st.scales[i, 0], st.scales[i, 1], qfmt)
 
 
 # ------------------------------------------------------------------ MLPFunction with fp8 compute
@@ -272,3 +459,129 @@ def mlp_fp8_backward(ctx, gy):
     for l in range(L):
         grads += [gW[l], gb[l]]
     return (dx, None, None, *grads)
+
+
+# ------------------------------------------------------------------ the same with delayed scaling
+def mlp_fp8_delayed_forward(ctx, x, slope, params, state: Fp8DelayedState):
+    """``mlp_fp8_forward`` under delayed scaling.  ``state`` holds three tensors per layer (3 l: the weight,
+    3 l + 1: the layer's input, 3 l + 2: the gradient of its output).  One ``update()`` launch opens the
+    step; weights go through the given-scale quantiser (one read each); layer l's GEMM emits layer l + 1's
+    quantised input with both copies from its epilogue, so an activation is never read back.  Only the
+    first FP8 layer's input is quantised by a launch of its own."""
+    from .gemm import _compute_weight, gemm
+
+    weights, biases = params[0::2], params[1::2]
+    L, cd = len(weights), torch.bfloat16
+    if any(state.seeded):
+        state.update()
+    h = x.detach().to(cd).contiguous()
+    hs, saved, kinds = [h], [], []
+    hq = None  # the quantised h, when the previous GEMM emitted it
+    for l in range(L):
+        last = l == L - 1
+        out_dtype = torch.float32 if last else cd
+        if fp8_layer(weights[l]):
+            wq = quantize_fp8(weights[l], "e4m3", transpose=True, scale=state.slot(3 * l))
+            if hq is None:
+                hq = quantize_fp8(h, "e4m3", transpose=True, scale=state.slot(3 * l + 1))
+            kw = dict(bias=biases[l].detach(), act=not last, slope=slope, out_dtype=out_dtype)
+            saved += [hq.data_t, hq.scale_inv, wq.data_t, wq.scale_inv]
+            if not last and fp8_layer(weights[l + 1]):
+                h, hq = gemm_fp8(hq, wq, quant_out=("e4m3", state.slot(3 * l + 4)), **kw)
+            else:
+                h, hq = gemm_fp8(hq, wq, **kw), None
+            kinds.append(True)
+        else:
+            w = _compute_weight(weights[l], cd)
+            h, hq = gemm(h, w, bias=biases[l].detach(), act=not last, slope=slope, out_dtype=out_dtype), None
+            saved.append(w)
+            kinds.append(False)
+        if not last:
+            hs.append(h)
+    ctx.save_for_backward(*hs, *saved)
+    ctx.params = [q if q.is_leaf else None for q in params]
+    ctx.L, ctx.slope, ctx.x_dtype, ctx.kinds = L, slope, x.dtype, kinds
+    ctx.x_needs = ctx.needs_input_grad[0]
+    ctx.fp8_state = state
+    return h
+
+
+def mlp_fp8_delayed_backward(ctx, gy):
+    """``mlp_fp8_backward`` under delayed scaling: the dx GEMM of layer l emits layer l - 1's e5m2 dz with
+    both copies; only the gradient entering the last FP8 layer is quantised by a launch of its own."""
+    from .gemm import _fused_grad_target, _grad_ready, colsum, gemm
+
+    L, slope, cd, state = ctx.L, ctx.slope, torch.bfloat16, ctx.fp8_state
+    saved = list(ctx.saved_tensors)
+    hs, rest = saved[:L], saved[L:]
+    per_layer = []
+    for k in ctx.kinds:
+        n = 4 if k else 1
+        per_layer.append(rest[:n])
+        rest = rest[n:]
+    dz = gy.to(cd).contiguous()
+    dq = None  # the quantised dz, when the previous dx GEMM emitted it
+    gW: list[torch.Tensor | None] = [None] * L
+    gb: list[torch.Tensor | None] = [None] * L
+    dx = None
+    need = ctx.needs_input_grad[3:]
+    for l in range(L - 1, -1, -1):
+        pw, pb = ctx.params[2 * l], ctx.params[2 * l + 1]
+        tw = _fused_grad_target(pw) if (pw is not None and need[2 * l]) else None
+        tb = _fused_grad_target(pb) if (pb is not None and need[2 * l + 1]) else None
+        if ctx.kinds[l]:
+            h_t, h_sinv, w_t, w_sinv = per_layer[l]
+            if dq is None:
+                dq = quantize_fp8(dz, "e5m2", transpose=True, scale=state.slot(3 * l + 2))
+            hT = Fp8Tensor(None, h_t, None, h_sinv, "e4m3")
+            wT = Fp8Tensor(None, w_t, None, w_sinv, "e4m3")
+            if tw is not None:
+                gemm_fp8(dq, hT, trans_a=True, trans_b=True, out=tw, accumulate=True)
+            else:
+                gW[l] = gemm_fp8(dq, hT, trans_a=True, trans_b=True, out_dtype=torch.float32)
+        elif tw is not None:
+            gemm(dz, hs[l], trans_a=True, trans_b=True, out=tw, accumulate=True)
+        else:
+            gW[l] = gemm(dz, hs[l], trans_a=True, trans_b=True, out_dtype=torch.float32)
+        if tb is not None:
+            colsum(dz, out=tb, accumulate=True)
+        else:
+            gb[l] = colsum(dz)
+        for q, t in ((pw, tw), (pb, tb)):
+            if t is not None:
+                _grad_ready(q)
+        if l > 0 or ctx.x_needs:
+            kw = dict(aux=hs[l], slope=slope, out_dtype=cd) if l > 0 else dict(out_dtype=torch.float32)
+            nq = None
+            if ctx.kinds[l] and l > 0 and ctx.kinds[l - 1]:
+                r, nq = gemm_fp8(dq, wT, trans_b=True, quant_out=("e5m2", state.slot(3 * l - 1)), **kw)
+            elif ctx.kinds[l]:
+                r = gemm_fp8(dq, wT, trans_b=True, **kw)
+            else:
+                r = gemm(dz, per_layer[l][0], trans_b=True, **kw)
+            dq = nq
+            if l > 0:
+                dz = r
+            else:
+                dx = r.to(ctx.x_dtype)
+    grads = []
+    for l in range(L):
+        grads += [gW[l], gb[l]]
+    return (dx, None, None, *grads)
+
+
+class MLPFp8DelayedFunction(torch.autograd.Function):
+    """``ops.gemm.MLPFunction`` with ``compute_dtype=torch.float8_e4m3fn`` and an ``Fp8DelayedState``."""
+
+    @staticmethod
+    def forward(ctx, x, slope, state, *params):
+        return mlp_fp8_delayed_forward(ctx, x, slope, params, state)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return mlp_fp8_delayed_backward(ctx, gy)
+
+
+def delayed_state_for(weights, history: int = 16) -> Fp8DelayedState:
+    """The state of an MLP with these weights: three tensors per layer, on the weights' device."""
+    return Fp8DelayedState(3 * len(weights), history, weights[0].device)

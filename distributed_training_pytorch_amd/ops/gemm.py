@@ -339,8 +339,16 @@ class MLPFunction(torch.autograd.Function):
 
 
 def mlp(x: torch.Tensor, weights: list[torch.Tensor], biases: list[torch.Tensor], slope: float = 0.01,
-        compute_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        compute_dtype: torch.dtype = torch.float32, fp8_state=None) -> torch.Tensor:
+    """``fp8_state``: an ``ops.fp8.Fp8DelayedState`` of three tensors per layer: with
+    ``compute_dtype=torch.float8_e4m3fn`` the FP8 layers then run the delayed-scaling recipe."""
     params = []
     for w, b in zip(weights, biases):
         params += [w, b]
+    if fp8_state is not None:
+        if compute_dtype != torch.float8_e4m3fn:
+            raise ValueError("mlp: fp8_state goes with compute_dtype=torch.float8_e4m3fn")
+        from .fp8 import MLPFp8DelayedFunction
+
+        return MLPFp8DelayedFunction.apply(x, slope, fp8_state, *params)
     return MLPFunction.apply(x, slope, compute_dtype, *params)

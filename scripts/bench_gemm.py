@@ -48,7 +48,7 @@ def fp8_layers(widths, batch, rounds, iters):
     on the FP8 kernel, both matrix instructions (f8f6f4 16x16x128 / fp8 16x16x32), interleaved
     with the bf16 kernels of the same build in one process: `rounds` rounds, medians.  Then the
     quantiser alone: GB/s against the bytes it moves (x read, q and qT written)."""
-    from distributed_training_pytorch_amd.ops.fp8 import gemm_fp8, quantize_fp8
+    from distributed_training_pytorch_amd.ops.fp8 import Fp8DelayedState, gemm_fp8, quantize_fp8
 
     def rnd(*shape):
         return torch.rand(*shape, device=DEV) * 2 - 1
@@ -65,6 +65,17 @@ def fp8_layers(widths, batch, rounds, iters):
             fns["fwd"][tag] = lambda m=m: gemm_fp8(hq, wq, bias=bias, act=True, mfma=m)
             fns["dx"][tag] = lambda m=m: gemm_fp8(dq, wq, trans_b=True, aux=h, mfma=m)
             fns["dW"][tag] = lambda m=m: gemm_fp8(dq, hq, trans_a=True, trans_b=True, out=dwf, accumulate=True, mfma=m)
+        # delayed scaling: the same GEMMs emitting their output quantised (both copies, amax) from the epilogue,
+        # and the given-scale quantiser launch that an unfused output would need instead
+        st = Fp8DelayedState(2, device=DEV)
+        st.set_scale(0, 448.0 / W, "e4m3")
+        st.set_scale(1, 57344.0 / W, "e5m2")
+        fns["fwd"]["fp8_x128_qout"] = lambda: gemm_fp8(hq, wq, bias=bias, act=True, quant_out=("e4m3", st.slot(0)))
+        fns["dx"]["fp8_x128_qout"] = lambda: gemm_fp8(dq, wq, trans_b=True, aux=h, quant_out=("e5m2", st.slot(1)))
+        fns["fwd"]["quantize_scaled"] = lambda: quantize_fp8(h, "e4m3", True, scale=st.slot(0))
+        fns["dx"]["quantize_scaled"] = lambda: quantize_fp8(dz, "e5m2", True, scale=st.slot(1))
+        fns["fwd"]["quantize_current"] = lambda: quantize_fp8(h, "e4m3", True)
+        fns["dx"]["quantize_current"] = lambda: quantize_fp8(dz, "e5m2", True)
         # the planned split-K dW (fp8_x128, where a plan exists) next to the same GEMM unsplit
         fns["dW"]["fp8_x128_unsplit"] = lambda: gemm_fp8(dq, hq, trans_a=True, trans_b=True, out=dwf, accumulate=True,
                                                          split_k=1)
@@ -77,7 +88,8 @@ def fp8_layers(widths, batch, rounds, iters):
             fl = 2.0 * batch * W * W
             print(json.dumps({"gemm": name, "W": W, "batch": batch, "rounds": rounds,
                               **{f"{k}_ms": round(v, 4) for k, v in med.items()},
-                              **{f"{k}_tflops": round(fl / v / 1e9, 1) for k, v in med.items()}}), flush=True)
+                              **{f"{k}_tflops": round(fl / v / 1e9, 1) for k, v in med.items()
+                                 if not k.startswith("quantize")}}), flush=True)
         for x, fmt in ((h, "e4m3"), (w, "e4m3"), (dz, "e5m2")):
             t = sorted(timeit(lambda: quantize_fp8(x, fmt, True), iters) for _ in range(rounds))[rounds // 2]
             nbytes = x.numel() * (x.element_size() + 2)

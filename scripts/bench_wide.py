@@ -37,8 +37,10 @@ def run_ours(a, X, Y, dev, world):
     from distributed_training_pytorch_amd.parallel.ddp import FlatDDP
 
     torch.manual_seed(0)
-    cd = {"fp8": torch.float8_e4m3fn, "mxfp8": torch.float8_e8m0fnu}.get(a.precision, torch.bfloat16)
-    bank = ModelBank(2, hidden=a.width, depth=a.depth, compute_dtype=cd).to(dev)
+    cd = {"fp8": torch.float8_e4m3fn, "fp8-delayed": torch.float8_e4m3fn,
+          "mxfp8": torch.float8_e8m0fnu}.get(a.precision, torch.bfloat16)
+    recipe = dict(fp8_recipe="delayed", fp8_amax_history=a.fp8_amax_history) if a.precision == "fp8-delayed" else {}
+    bank = ModelBank(2, hidden=a.width, depth=a.depth, compute_dtype=cd, **recipe).to(dev)
     ddp = FlatDDP(bank, flat_params=bank.flat, flat_grad=bank.flat_grad, comm="rccl") if world > 1 else None
     # --shadow: Adam also writes the bf16 weight operands (no per-forward casts). Measured
     # at W = 4096 / 2048 / 1024: 4.52 / 1.78 / 1.28 ms vs 4.56 / 1.75 / 1.28 casting each
@@ -100,10 +102,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--impl", choices=["ours", "stock", "both"], default="both")
-    ap.add_argument("--precision", choices=["bf16", "fp8", "mxfp8"], default="bf16",
+    ap.add_argument("--precision", choices=["bf16", "fp8", "fp8-delayed", "mxfp8"], default="bf16",
                     help="ours: bf16 layer GEMMs, or fp8 (ops/fp8.py: e4m3 x e4m3 forward, e5m2 x e4m3 backward, "
-                         "per-tensor scales; the hidden width must be a multiple of 16), or mxfp8 (ops/mxfp8.py: e4m3 "
+                         "per-tensor scales; the hidden width must be a multiple of 16), or fp8-delayed (fp8 with scales "
+                         "from an amax history, operands emitted by the GEMM epilogues), or mxfp8 (ops/mxfp8.py: e4m3 "
                          "throughout, one E8M0 scale per 32 elements; a multiple of 32)")
+    ap.add_argument("--fp8_amax_history", type=int, default=16)
     ap.add_argument("--shadow", action="store_true",
                     help="ours: the Adam kernel writes the bf16 weight operands (ops/gemm.py ComputeShadow) "
                          "instead of a cast before every forward")
