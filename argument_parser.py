@@ -71,6 +71,9 @@ def build_parser(description: str | None = None) -> argparse.ArgumentParser:
     p.add_argument("--depth", type=int, default=3, help="number of hidden Linear(h,h) layers")
     p.add_argument("--fp8_amax_history", type=int, default=16,
                    help="--precision fp8-delayed: amaxes kept per tensor; its scale is fmax over their maximum (1..1024)")
+    p.add_argument("--fp8_shadow", action="store_true",
+                   help="--precision fp8-delayed only: the flat optimizer's launch also writes the e4m3 weight operands "
+                        "(ops.fp8.Fp8WeightShadow), so no forward quantises a weight; the same bits as without it")
     p.add_argument("--precision", choices=["fp32", "bf16", "fp8", "fp8-delayed", "mxfp8"], default="fp32",
                    help="fp32 = the reference (precision=32); bf16 = bf16 matmul operands with fp32 "
                         "accumulation, fp32 master weights and optimizer (fused toy kernels have bf16 "

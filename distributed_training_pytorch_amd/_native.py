@@ -291,6 +291,41 @@ class Fp8ScaleRec(ctypes.Structure):  # DtpFp8ScaleRec
     ]
 
 
+class Fp8ShadowRec(ctypes.Structure):  # DtpFp8ShadowRec
+    _fields_ = [
+        ("scale", c_void_p),
+        ("partials", c_void_p),
+        ("used", c_void_p),
+        ("q", c_void_p),
+        ("qT", c_void_p),
+        ("offset", c_longlong),
+        ("out", c_int),
+        ("in_", c_int),
+        ("cap", c_int),
+        ("pad_", c_int),
+    ]
+
+
+class Fp8WorkItem(ctypes.Structure):  # DtpFp8WorkItem
+    _fields_ = [
+        ("rec", c_int),
+        ("a", c_int),
+        ("b", c_int),
+        ("model", c_int),
+        ("first", c_int),
+        ("pad_", c_int * 3),
+    ]
+
+
+class Fp8ShadowWork(ctypes.Structure):  # DtpFp8ShadowWork
+    _fields_ = [
+        ("recs", c_void_p),
+        ("items", c_void_p),
+        ("n_items", c_int),
+        ("pad_", c_int),
+    ]
+
+
 class GemmMxArgs(ctypes.Structure):
     _fields_ = [
         ("A", c_void_p),
@@ -378,6 +413,7 @@ def _declare(lib):
         "dtp_mlp_stage_fwd_multi": (c_int, [P(StageMulti), c_int, c_int, c_int, c_int, c_int, c_void_p]),
         "dtp_mlp_stage_bwd": (c_int, [P(StageArgs), c_int, c_int, c_int, c_int, c_int, c_void_p]),
         "dtp_flat_optimizer": (c_int, [P(OptArgs), c_void_p]),
+        "dtp_flat_optimizer_fp8": (c_int, [P(OptArgs), P(Fp8ShadowRec), c_int, P(Fp8ShadowWork), c_void_p]),
         "dtp_grad_norm": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),
         "dtp_grad_norm_ws_bytes": (c_longlong, [c_int]),
         "dtp_clip_grad_norm": (c_int, [c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p]),

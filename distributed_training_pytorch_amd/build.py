@@ -48,7 +48,9 @@ SOURCE_FLAGS = {**{s: ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-ffp-contrac
                 # the FP8 sources: no packed-fp32 VALU forms (v_pk_mul_f32 and kin) in the scale /
                 # epilogue math, so the quantiser rounds exactly as its torch definition does
                 **{s: ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-                   for s in ("fp8_quant.hip", "gemm_fp8.hip", "mxfp8_quant.hip", "gemm_mxfp8.hip")}}
+                   for s in ("fp8_quant.hip", "gemm_fp8.hip", "mxfp8_quant.hip", "gemm_mxfp8.hip")},
+                # the optimizer that also quantises its weights: both rules at once
+                "optim_fp8.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def hipcc() -> str:

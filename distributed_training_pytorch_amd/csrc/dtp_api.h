@@ -356,6 +356,41 @@ int dtp_gemm_fp8_quant(const DtpGemmFp8Args* a, const DtpFp8QuantOut* qo, void* 
 // bytes of DtpGemmFp8Args::work the call would use with splitk = 0 (0: no split-K plan); host only
 long long dtp_gemm_fp8_workspace(const DtpGemmFp8Args* a);
 
+// -- the flat optimizer that also emits the e4m3 weight operands of the delayed recipe (optim_fp8.hip) --
+// One record per shadowed weight: a contiguous [out][in] matrix inside one row of the flat [n_models][P]
+// buffers, both widths multiples of 16.  The launch that updates it writes q = cvt_rne(clamp(p_new * *scale,
+// +-448)) row-major and transposed, the |p_new| amax of every 64 x 64 tile into `partials` (the layout of
+// DtpFp8ScaleRec::partials: word 0 the tile count) and {scale[0], scale[1]} as it read them into `used`.
+struct DtpFp8ShadowRec {
+  const float* scale;   // [2] device: the slot's scale and 1 / scale
+  unsigned* partials;   // [1 + cap]
+  float* used;          // [2]
+  void* q;              // [out][in] e4m3, 16-byte aligned
+  void* qT;             // [in][out] e4m3, 16-byte aligned
+  long long offset;     // of element (0, 0) in the flat buffers: model * P + column
+  int out, in;
+  int cap;
+  int pad_;
+};
+// One workgroup's work.  rec >= 0: tile `a` (row-major over ceil(out / 64) x ceil(in / 64)) of that record.
+// rec < 0: the element-wise update of columns [a, a + b) of row `model` (everything that is no shadowed weight).
+struct DtpFp8WorkItem {
+  int rec, a, b, model;
+  int first;  // 1 on one item per model: it publishes the row's loss-log entry and norm
+  int pad_[3];
+};
+struct DtpFp8ShadowWork {
+  const DtpFp8ShadowRec* recs;  // the records again, on the device
+  const DtpFp8WorkItem* items;  // device
+  int n_items;
+  int pad_;
+};
+// dtp_flat_optimizer (a->shadow must be null) as one launch over the work items, then the step counters.
+// `recs` is the host copy, checked here; clipping by norm launches the norm first (its partials for rows of
+// more than 4096 elements, else the finished norm into norm_out).
+int dtp_flat_optimizer_fp8(const DtpOptArgs* a, const DtpFp8ShadowRec* recs, int n_recs, const DtpFp8ShadowWork* work,
+                           void* stream);
+
 // ---- MXFP8: FP8 with one E8M0 scale byte per 32 elements along K (mxfp8_quant.hip, gemm_mxfp8.hip) ----
 // Block-scaled cast of x [M][ldx] (f32 or bf16, K % 32 == 0, finite).  For each block of 32 along K with
 // a = max|x|: scale byte sb = a == 0 ? 127 : max(expfield(a) - emax, 0) (emax 8 e4m3 / 15 e5m2), elements

@@ -12,85 +12,14 @@
 #include "dtp_api.h"
 #include <type_traits>
 #include "optim_core.h"
+#include "optim_norm.h"
 
 namespace dtp {
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
-// ---- per-row gradient norm (clip by norm) ----
-// The squares are summed in fp64 (a float squared is exact there) in an order fixed by P
-// alone: every thread's chains, the xor butterfly within a wave (every lane ends with the
-// same tree), the four waves as (w0 + w1) + (w2 + w3), and the per-block partials by the
-// same block sum again.  No floating-point atomics: the norm is bitwise the same from run
-// to run, in every block that forms it, and on every data-parallel replica.
-constexpr int kNormUnroll = 4;                            // float4 loads in flight per thread
-constexpr int kNormChunk = kNormUnroll * 4 * kBlock;      // elements per block and grid-stride iteration
-constexpr int kNormMaxBlocks = 256;                       // per row: one block per CU, <= kBlock partials
-constexpr int kOneBlockP = 16 * kBlock;                   // rows up to this take one block (norm + update fused)
-
-__host__ __device__ inline int norm_blocks(int P) {
-  const int nb = (P + kNormChunk - 1) / kNormChunk;
-  return nb < kNormMaxBlocks ? nb : kNormMaxBlocks;
-}
-
-DTP_DEV double block_sum(double v) {
-  __shared__ double wsum[kBlock / kWave];
-#pragma unroll
-  for (int o = kWave / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-  __syncthreads();
-  if ((threadIdx.x & (kWave - 1)) == 0) wsum[threadIdx.x / kWave] = v;
-  __syncthreads();
-  return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
-// this thread's share of sum((g[i] * gs)^2) over one row, as block `blk` of `nblk`.
-// float4 loads with the update's head / tail treatment (an odd P leaves row 1 off a
-// 16-byte boundary); the head and tail elements go to the first block's first threads.
-DTP_DEV double row_sumsq(const float* g, int P, float gs, int blk, int nblk) {
-  const uintptr_t ph = (uintptr_t)g & 15;
-  const int head = min((int)((16 - ph) & 15) >> 2, P);
-  const int P4 = (P - head) >> 2, tail0 = head + 4 * P4;
-  const float4* g4 = reinterpret_cast<const float4*>(g + head);
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  for (long long base = (long long)blk * (kNormUnroll * kBlock); base < P4; base += (long long)nblk * (kNormUnroll * kBlock)) {
-    float4 q[kNormUnroll];
-#pragma unroll
-    for (int u = 0; u < kNormUnroll; ++u) {
-      const long long i = base + u * kBlock + threadIdx.x;
-      q[u] = i < P4 ? g4[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-    for (int u = 0; u < kNormUnroll; ++u) {
-      const double x = (double)(q[u].x * gs), y = (double)(q[u].y * gs), z = (double)(q[u].z * gs), w = (double)(q[u].w * gs);
-      a0 = fma(x, x, a0);
-      a1 = fma(y, y, a1);
-      a2 = fma(z, z, a2);
-      a3 = fma(w, w, a3);
-    }
-  }
-  const int e = blk == 0 ? (int)threadIdx.x : 1 << 30;
-  const int idx = e < head ? e : (e - head < P - tail0 ? tail0 + e - head : -1);
-  if (idx >= 0) {
-    const double x = (double)(g[idx] * gs);
-    a0 = fma(x, x, a0);
-  }
-  return (a0 + a1) + (a2 + a3);
-}
-
-// the row's sum of squares from its nb (<= kNormMaxBlocks <= kBlock) per-block partials
-DTP_DEV double partials_sum(const double* ws, int nb) {
-  static_assert(kNormMaxBlocks <= kBlock, "one partial per thread");
-  return block_sum((int)threadIdx.x < nb ? ws[threadIdx.x] : 0.0);
-}
-
-// the whole block ends with the same value: the row's L2 norm.  ws == null: this block
-// reads the whole row itself (one-block rows), else the norm kernel's partials.
-DTP_DEV float row_norm(const float* g, int P, float gs, const double* ws) {
-  const double s = ws ? partials_sum(ws, norm_blocks(P)) : block_sum(row_sumsq(g, P, gs, 0, 1));
-  return (float)sqrt(s);
-}
-
+// ---- per-row gradient norm (clip by norm): the sums are in optim_norm.h ----
 __global__ __launch_bounds__(kBlock) void grad_norm_partial_kernel(const float* grad, int P, float gs, double* ws) {
   const double s = block_sum(row_sumsq(grad + (size_t)blockIdx.y * P, P, gs, blockIdx.x, gridDim.x));
   if (threadIdx.x == 0) ws[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
@@ -291,15 +220,26 @@ __global__ void advance_steps_kernel(int* step, int n) {
 
 }  // namespace dtp
 
+namespace dtp {
+void launch_norm_partials(const float* grad, int n_models, int P, float scale, double* ws, hipStream_t st) {
+  hipLaunchKernelGGL(grad_norm_partial_kernel, dim3(norm_blocks(P), n_models), dim3(kBlock), 0, st, grad, P, scale, ws);
+}
+
+void launch_norm_finish(const float* grad, int n_models, int P, float scale, const double* ws, float* out, hipStream_t st) {
+  hipLaunchKernelGGL(grad_norm_finish_kernel, dim3(1, n_models), dim3(kBlock), 0, st, grad, P, scale, ws, out);
+}
+
+// one thread per model: a single 64-thread block left the counters of models 64.. at
+// their old step (those models then kept the first step's bias correction)
+void launch_advance_steps(int* step, int n_models, hipStream_t st) {
+  hipLaunchKernelGGL(advance_steps_kernel, dim3((n_models + 63) / 64), dim3(64), 0, st, step, n_models);
+}
+}  // namespace dtp
+
 namespace {
 using dtp::check_launch;
+using dtp::launch_norm_partials;
 using dtp::set_err;
-
-// rows of more than kOneBlockP elements: per-block fp64 partials into ws, [n_models][norm_blocks(P)]
-void launch_norm_partials(const float* grad, int n_models, int P, float scale, double* ws, hipStream_t st) {
-  hipLaunchKernelGGL(dtp::grad_norm_partial_kernel, dim3(dtp::norm_blocks(P), n_models), dim3(dtp::kBlock), 0, st, grad, P,
-                     scale, ws);
-}
 }  // namespace
 
 extern "C" long long dtp_grad_norm_ws_bytes(int P) {
@@ -312,8 +252,7 @@ extern "C" int dtp_grad_norm(const float* grad, int n_models, int P, float scale
   if (multi && !ws) return set_err(-5, "grad_norm: rows of more than 4096 elements need the workspace");
   hipStream_t st = (hipStream_t)stream;
   if (multi) launch_norm_partials(grad, n_models, P, scale, ws, st);
-  hipLaunchKernelGGL(dtp::grad_norm_finish_kernel, dim3(1, n_models), dim3(dtp::kBlock), 0, st, grad, P, scale,
-                     multi ? (const double*)ws : nullptr, out);
+  dtp::launch_norm_finish(grad, n_models, P, scale, multi ? (const double*)ws : nullptr, out, st);
   return check_launch("grad_norm_kernel");
 }
 
@@ -355,9 +294,6 @@ extern "C" int dtp_flat_optimizer(const DtpOptArgs* a, void* stream) {
   } else {
     hipLaunchKernelGGL(dtp::flat_optimizer_kernel, grid, block, 0, st, *a);
   }
-  // one thread per model: a single 64-thread block left the counters of models 64.. at
-  // their old step (those models then kept the first step's bias correction)
-  if (nblk > 1)
-    hipLaunchKernelGGL(dtp::advance_steps_kernel, dim3((a->n_models + 63) / 64), dim3(64), 0, st, a->step, a->n_models);
+  if (nblk > 1) dtp::launch_advance_steps(a->step, a->n_models, st);
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -115,6 +115,16 @@ def _fp8_recipe(config) -> dict:
     return {"fp8_recipe": "delayed", "fp8_amax_history": int(getattr(config, "fp8_amax_history", 16))}
 
 
+def _fp8_shadow(config) -> bool:
+    """--fp8_shadow: the optimizer writes the FP8 weight operands; the delayed recipe's only (a scale known
+    before the weight is)."""
+    if not getattr(config, "fp8_shadow", False):
+        return False
+    if getattr(config, "precision", "fp32") != "fp8-delayed":
+        raise ValueError(f"--fp8_shadow goes with --precision fp8-delayed (got --precision {config.precision})")
+    return True
+
+
 def _fused_supported(config) -> bool:
     from .. import _native as nat
     from ..ops.mlp import MlpSpec
@@ -264,6 +274,7 @@ def train(config, env, device, rank, world, group: str = "base-demo") -> dict:
     t_start = time.perf_counter()
     engine = config.engine
     fp8 = _compute_dtype(config) in _FP8_DTYPES  # (raises on a width the FP8 / MXFP8 path cannot take)
+    _fp8_shadow(config)  # (raises with any other precision)
     if engine == "fused" and (device.type == "cuda" or fp8) and not _fused_supported(config):
         # widths / dtypes the fused step kernel is not instantiated for train through
         # nn.Modules whose Linears run on the MFMA GEMM (FlatDDP + FlatOptimizer)
@@ -302,6 +313,8 @@ def train(config, env, device, rank, world, group: str = "base-demo") -> dict:
     if fp8 and _compute_dtype(config) == torch.float8_e4m3fn:  # the per-tensor scaling recipe that ran
         r = _fp8_recipe(config)
         summary["fp8_recipe"] = f"delayed (amax history {r['fp8_amax_history']})" if r else "current"
+        if _fp8_shadow(config):
+            summary["fp8_weight_shadow"] = True
     rank_print(rank, "Finished")
     return summary
 
@@ -435,7 +448,8 @@ def _train_module(config, device, rank, world, logger, faults) -> dict:
                   comm=config.comm if config.comm in ("auto", "rccl", "xgmi") else "rccl")
     rank_print(rank, f"engine: module (FlatDDP over {ddp.comm})")
     from .graph_step import CapturedStep
-    opt = FlatOptimizer(bank.flat, bank.flat_grad, _optim(config))
+    opt = FlatOptimizer(bank.flat, bank.flat_grad, _optim(config),
+                        shadow=bank.fp8_shadow() if _fp8_shadow(config) else None)
     lossf = torch.nn.CrossEntropyLoss() if config.loss == "ce" else MSELoss()  # fused drop-in (ops/loss.py)
     # gradient accumulation, the plain form: A micro-batches per optimizer step, each loss scaled
     # by 1/A through the backward seed, the first A - 1 backwards under ddp.no_sync(), one

@@ -49,6 +49,30 @@ class ModelBank(nn.Module):
         if getattr(self, "_shadow", None) is not None:  # the old shadow's views point at the old buffer
             self._shadow.detach_()
             self._shadow = None
+        if getattr(self, "_fp8_shadow", None) is not None:
+            self._fp8_shadow.detach_()
+            self._fp8_shadow = None
+
+    def fp8_shadow(self):
+        """An ``ops.fp8.Fp8WeightShadow`` of every weight matrix that runs on the FP8 GEMM, for
+        ``FlatOptimizer(..., shadow=bank.fp8_shadow())``: the optimizer then writes the e4m3 weight
+        operands of the delayed-scaling recipe and the forward quantises no weight.  Makes each
+        model's delayed state if the first forward has not yet.  Rebuilt after ``.to()`` / ``rebind()``."""
+        from ..ops.fp8 import Fp8WeightShadow, fp8_layer
+
+        if any(m.compute_dtype != torch.float8_e4m3fn or m.fp8_recipe != "delayed" for m in self.models):
+            raise ValueError("ModelBank.fp8_shadow: needs compute_dtype=torch.float8_e4m3fn with fp8_recipe='delayed'")
+        if getattr(self, "_fp8_shadow", None) is None:
+            weights, slots = [], []
+            for m in self.models:
+                ws = [layer.weight for layer in m.layers if isinstance(layer, nn.Linear)]
+                state = m._fp8_state(ws)
+                for l, w in enumerate(ws):
+                    if fp8_layer(w):
+                        weights.append(w)
+                        slots.append(state.slot(3 * l))
+            self._fp8_shadow = Fp8WeightShadow(self.flat, weights, slots)
+        return self._fp8_shadow
 
     def compute_shadow(self):
         """A bf16 ``ComputeShadow`` of the bank's weight matrices (the GEMM path's

@@ -159,8 +159,148 @@ def fp8_amax(x: torch.Tensor, slot: Fp8Slot) -> None:
                                nat.stream_ptr()), "dtp_fp8_amax")
 
 
-def _quantize_given(x: torch.Tensor, fmt: str, transpose: bool, slot: Fp8Slot) -> Fp8Tensor:
-    """``cvt(clamp(x * scale, -fmax, fmax))`` with the slot's scale; the slot's partials receive amax|x|."""
+_SPAN_CHUNK = 4096  # elements per span item of a shadow's work table (16 per thread)
+
+
+class Fp8WeightShadow:
+    """The e4m3 operands of weight matrices inside a flat fp32 parameter buffer, written by the optimizer.
+
+    Under delayed scaling a weight's scale is known before the weight is, so the flat optimizer's launch
+    (``csrc/optim_fp8.hip``, ``flat_optimizer_step(shadow=...)``) also writes, per weight, ``q = cvt(clamp(
+    p_new * scale, +-448))`` [out, in], its transpose ``qT`` [in, out], amax|p_new| into the slot's partials
+    and the ``{scale, 1 / scale}`` it read into ``used``: the slot's scale is formed again by the next
+    ``Fp8DelayedState.update()``, before the forward's GEMM reads the operand, so the operand carries the
+    scale it was written with.  ``mlp_fp8_delayed_forward`` then takes ``operand(w)`` and launches no
+    quantiser for ``w``.
+
+    ``weights``: contiguous 2-D views of one row of ``flat`` each, both widths multiples of 16; ``slots``:
+    their ``Fp8Slot``s.  Staleness is ``ops.gemm.ComputeShadow``'s rule: the operands are trusted only while
+    the version counters of ``flat`` and of every weight are the ones recorded at ``mark_fresh()``; any torch
+    in-place write makes ``operand`` return None until the optimizer has written again.  On a stale weight the
+    forward quantises by a launch, with the scale in ``used`` once the optimizer has written one (the scale
+    the operand it replaces was written with), else with the slot's."""
+
+    def __init__(self, flat: torch.Tensor, weights, slots):
+        weights, slots = list(weights), list(slots)
+        if flat.dtype != torch.float32 or not flat.is_contiguous() or flat.dim() not in (1, 2):
+            raise ValueError("Fp8WeightShadow: a contiguous fp32 flat buffer")
+        if not weights or len(weights) != len(slots):
+            raise ValueError("Fp8WeightShadow: one slot per weight, at least one weight")
+        self.flat, self.weights, self.slots = flat, weights, slots
+        rows = flat if flat.dim() == 2 else flat.view(1, -1)
+        n, P = rows.shape
+        self._offsets = []
+        dev = flat.device
+        for w, s in zip(weights, slots):
+            if not isinstance(s, Fp8Slot) or s.state.device != dev:
+                raise ValueError("Fp8WeightShadow: every weight needs an Fp8Slot of a state on the buffer's device")
+            off = (w.data_ptr() - flat.data_ptr()) // 4
+            if (w.dim() != 2 or w.dtype != torch.float32 or not w.is_contiguous() or w.device != dev or off < 0
+                    or off + w.numel() > n * P or off // P != (off + w.numel() - 1) // P):
+                raise ValueError("Fp8WeightShadow: every weight must be a contiguous 2-D view of one flat row")
+            if not fp8_layer(w) or 0 in w.shape:
+                raise ValueError(f"Fp8WeightShadow: both widths must be multiples of 16, got {tuple(w.shape)}")
+            if -(-w.shape[0] // 64) * -(-w.shape[1] // 64) > _PART_CAP:
+                raise ValueError(f"Fp8WeightShadow: {tuple(w.shape)} has more 64 x 64 tiles than the {_PART_CAP} partials")
+            s.state.bind(s.index, "e4m3")
+            self._offsets.append(off)
+        self.q = [torch.zeros(w.shape, dtype=torch.float8_e4m3fn, device=dev) for w in weights]
+        self.qT = [torch.zeros(w.shape[::-1], dtype=torch.float8_e4m3fn, device=dev) for w in weights]
+        self.used = [torch.ones(2, dtype=torch.float32, device=dev) for _ in weights]
+        for i, w in enumerate(weights):
+            w._dtp_fp8_shadow = (self, i)
+        self._token, self.written, self.served = None, False, 0
+        self._recs = self._work = None
+        if dev.type == "cuda" and nat.native_enabled():
+            self._build_table(n, P)
+
+    def _build_table(self, n: int, P: int) -> None:
+        """The records (host copy for the entry's checks, device copy for the kernel) and the work items:
+        per row, the tiles of its weights and the columns between them in chunks."""
+        import ctypes
+
+        recs = (nat.Fp8ShadowRec * len(self.weights))()
+        for i, (w, (st, k)) in enumerate(zip(self.weights, self.slots)):
+            r = recs[i]
+            r.scale, r.partials, r.used = nat.ptr(st.scales[k]), nat.ptr(st.partials[k]), nat.ptr(self.used[i])
+            r.q, r.qT, r.offset = nat.ptr(self.q[i]), nat.ptr(self.qT[i]), self._offsets[i]
+            r.out, r.in_, r.cap = w.shape[0], w.shape[1], _PART_CAP
+        items = []
+        for model in range(n):
+            col = 0
+            mine = sorted((off - model * P, i) for i, off in enumerate(self._offsets) if off // P == model)
+            for c, i in [*mine, (P, None)]:
+                if c < col:
+                    raise ValueError("Fp8WeightShadow: the weights overlap")
+                items += [(-1, s, min(_SPAN_CHUNK, c - s), model) for s in range(col, c, _SPAN_CHUNK)]
+                if i is not None:
+                    out, k = self.weights[i].shape
+                    items += [(i, t, 0, model) for t in range(-(-out // 64) * -(-k // 64))]
+                    col = c + out * k
+        table = (nat.Fp8WorkItem * len(items))()
+        seen = set()
+        for it, (rec, a, b, model) in zip(table, items):
+            it.rec, it.a, it.b, it.model, it.first = rec, a, b, model, int(model not in seen)
+            seen.add(model)
+        dev = self.flat.device
+        self._host_recs, self._n_items = recs, len(items)
+        self._recs = torch.frombuffer(bytearray(bytes(recs)), dtype=torch.uint8).to(dev)
+        self._items = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+        self._work = nat.Fp8ShadowWork(nat.ptr(self._recs), nat.ptr(self._items), len(items), 0)
+        assert ctypes.sizeof(nat.Fp8WorkItem) == 32 and ctypes.sizeof(nat.Fp8ShadowRec) == 64
+
+    def _current(self):
+        return (self.flat._version, *(w._version for w in self.weights))
+
+    def seeded(self) -> bool:
+        """Does every weight's slot hold a scale?  (The first step seeds them in the forward.)"""
+        return all(st.seeded[k] for st, k in self.slots)
+
+    def step_native(self, lib, args) -> None:
+        """``dtp_flat_optimizer_fp8`` with this shadow's records and work table."""
+        import ctypes
+
+        nat.check(lib.dtp_flat_optimizer_fp8(ctypes.byref(args), self._host_recs, len(self.weights), ctypes.byref(self._work),
+                                             nat.stream_ptr()), "dtp_flat_optimizer_fp8")
+        self.written = True
+
+    def write_ref(self) -> None:
+        """What the kernel writes besides the update, by the torch definition (CPU tensors)."""
+        for i, (w, (st, k)) in enumerate(zip(self.weights, self.slots)):
+            x = w.detach().float()
+            q = (x * st.scales[k, 0]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
+            self.q[i].copy_(q)
+            self.qT[i].copy_(q.t())
+            st.partials[k, 1] = x.abs().max().view(torch.int32)
+            st.partials[k, 0] = 1
+            self.used[i].copy_(st.scales[k])
+        self.written = True
+
+    def operand(self, w: torch.Tensor) -> Fp8Tensor | None:
+        """The optimizer-written operand of ``w`` if it is fresh, else None."""
+        sh = getattr(w, "_dtp_fp8_shadow", None)
+        if sh is None or sh[0] is not self or self._token != self._current():
+            return None
+        i = sh[1]
+        self.served += 1
+        return Fp8Tensor(self.q[i], self.qT[i], self.used[i][0], self.used[i][1], "e4m3")
+
+    def used_scales(self, w: torch.Tensor) -> torch.Tensor | None:
+        """``{scale, 1 / scale}`` of the last operand the optimizer wrote for ``w`` (None before the first)."""
+        return self.used[w._dtp_fp8_shadow[1]] if self.written else None
+
+    def mark_fresh(self) -> None:
+        self._token = self._current()
+
+    def detach_(self) -> None:
+        for w in self.weights:
+            if getattr(w, "_dtp_fp8_shadow", (None,))[0] is self:
+                del w._dtp_fp8_shadow
+
+
+def _quantize_given(x: torch.Tensor, fmt: str, transpose: bool, slot: Fp8Slot, scales: torch.Tensor | None = None) -> Fp8Tensor:
+    """``cvt(clamp(x * scale, -fmax, fmax))`` with the slot's scale (``scales``: this ``{scale, 1 / scale}``
+    pair instead); the slot's partials receive amax|x|."""
     st, i = slot
     dtype, fmax, code = _FMT[fmt]
     st.bind(i, fmt)
@@ -176,7 +316,7 @@ def _quantize_given(x: torch.Tensor, fmt: str, transpose: bool, slot: Fp8Slot) -
         st.seeded[i] = True
     M, K = x.shape
     Mp = -(-M // 16) * 16
-    scale, scale_inv = st.scales[i, 0], st.scales[i, 1]
+    scale, scale_inv = (st.scales[i, 0], st.scales[i, 1]) if scales is None else (scales[0], scales[1])
     if x.device.type != "cuda" or not nat.native_enabled():
         q = (x.float() * scale).clamp(-fmax, fmax).to(dtype)
         qt = None
@@ -467,7 +607,8 @@ def mlp_fp8_delayed_forward(ctx, x, slope, params, state: Fp8DelayedState):
     3 l + 1: the layer's input, 3 l + 2: the gradient of its output).  One ``update()`` launch opens the
     step; weights go through the given-scale quantiser (one read each); layer l's GEMM emits layer l + 1's
     quantised input with both copies from its epilogue, so an activation is never read back.  Only the
-    first FP8 layer's input is quantised by a launch of its own."""
+    first FP8 layer's input is quantised by a launch of its own.  A weight with a fresh ``Fp8WeightShadow``
+    is not quantised here at all: the optimizer wrote its operand."""
     from .gemm import _compute_weight, gemm
 
     weights, biases = params[0::2], params[1::2]
@@ -481,7 +622,13 @@ def mlp_fp8_delayed_forward(ctx, x, slope, params, state: Fp8DelayedState):
         last = l == L - 1
         out_dtype = torch.float32 if last else cd
         if fp8_layer(weights[l]):
-            wq = quantize_fp8(weights[l], "e4m3", transpose=True, scale=state.slot(3 * l))
+            # the optimizer-written operand while it is fresh (Fp8WeightShadow): no quantiser launch
+            sh = getattr(weights[l], "_dtp_fp8_shadow", (None,))[0]
+            wq = sh.operand(weights[l]) if sh is not None else None
+            if wq is None and sh is not None and sh.used_scales(weights[l]) is not None and state.seeded[3 * l]:
+                wq = _quantize_given(weights[l], "e4m3", True, state.slot(3 * l), sh.used_scales(weights[l]))
+            elif wq is None:
+                wq = quantize_fp8(weights[l], "e4m3", transpose=True, scale=state.slot(3 * l))
             if hq is None:
                 hq = quantize_fp8(h, "e4m3", transpose=True, scale=state.slot(3 * l + 1))
             kw = dict(bias=biases[l].detach(), act=not last, slope=slope, out_dtype=out_dtype)

@@ -285,10 +285,20 @@ def flat_optimizer_step(params, m, v, step, grad, cfg: OptimConfig, grad_scale: 
     Both are allocated here when missing -- pass them for a step under graph capture.  A
     clipped step launches ``fused`` backwards first: the norm needs the finished gradient.
     """
+    from .fp8 import Fp8WeightShadow
+
     n_models, P = params.shape
     if cfg.max_grad_norm > 0 and cfg.clip_grad_value > 0:
         raise ValueError("flat_optimizer_step: max_grad_norm and clip_grad_value are exclusive")
     by_norm = cfg.max_grad_norm > 0
+    # an Fp8WeightShadow: the launch also writes the e4m3 weight operands (csrc/optim_fp8.hip) once every
+    # slot holds a scale; before that (the first step: the forward seeds them) this is the plain step
+    fp8sh, shadow = (shadow, None) if isinstance(shadow, Fp8WeightShadow) else (None, shadow)
+    if fp8sh is not None:
+        if fp8sh.flat.data_ptr() != params.data_ptr() or fp8sh.flat.numel() != params.numel():
+            raise ValueError("flat_optimizer_step: the FP8 shadow must be of these parameters")
+        if not fp8sh.seeded():
+            fp8sh = None
     if shadow is not None and (shadow.dtype != torch.bfloat16 or shadow.dim() != 2 or shadow.shape[0] != n_models
                                or shadow.shape[1] < P or shadow.stride(1) != 1 or shadow.device != params.device):
         raise ValueError("flat_optimizer_step: shadow must be a bf16 [n_models, >= P] tensor with unit column stride")
@@ -305,10 +315,14 @@ def flat_optimizer_step(params, m, v, step, grad, cfg: OptimConfig, grad_scale: 
                         0 if shadow is None else shadow.stride(0), max(cfg.max_grad_norm, 0.0),
                         max(cfg.clip_grad_value, 0.0), nat.ptr(norm_ws) if by_norm else None,
                         nat.ptr(norm_out) if by_norm else None)
-        if fused is not None and cfg.clips:
+        if fused is not None and (cfg.clips or fp8sh is not None):
             for p in fused:
                 p.launch()
             fused = None
+        if fp8sh is not None:
+            fp8sh.step_native(lib, a)
+            fp8sh.mark_fresh()
+            return
         if fused is not None:  # the stage backwards that produced `grad`, in the same launch
             from .mlp import launch_fused_with_optimizer
 
@@ -340,6 +354,9 @@ def flat_optimizer_step(params, m, v, step, grad, cfg: OptimConfig, grad_scale: 
         grad[: n_models * P].zero_()
     if shadow is not None:
         shadow[:, :P].copy_(params)
+    if fp8sh is not None:  # the torch definition of what the kernel writes
+        fp8sh.write_ref()
+        fp8sh.mark_fresh()
 
 
 class FlatOptimizer:
@@ -354,8 +371,13 @@ class FlatOptimizer:
     def __init__(self, flat_params: torch.Tensor, flat_grad: torch.Tensor, cfg: OptimConfig | None = None,
                  slope: float = 0.01, shadow=None):
         """``shadow``: an ``ops.gemm.ComputeShadow`` of ``flat_params``; every step also
-        writes its bf16 copy (the bf16-compute forward then needs no weight casts)."""
+        writes its bf16 copy (the bf16-compute forward then needs no weight casts).  Or an
+        ``ops.fp8.Fp8WeightShadow`` of it (``ModelBank.fp8_shadow()``): every step but the first
+        also writes the e4m3 weight operands of the delayed-scaling recipe."""
+        from .fp8 import Fp8WeightShadow
+
         self.shadow = shadow
+        self._fp8_shadow = isinstance(shadow, Fp8WeightShadow)
         if shadow is not None and shadow.flat.data_ptr() != flat_params.data_ptr():
             raise ValueError("FlatOptimizer: the shadow must be of flat_params")
         self.params = flat_params if flat_params.dim() == 2 else flat_params.view(1, -1)
@@ -387,6 +409,8 @@ class FlatOptimizer:
         n, P = self.params.shape
         sh = self.shadow
         fresh = sh is not None and sh._token == sh._current()  # else the next forward re-casts anyway
+        if self._fp8_shadow:  # written whenever its scales exist: a stale one is fresh again after this step
+            fresh = sh.seeded()
         if fused is not None:
             from .mlp import fused_rows_match
 
@@ -401,9 +425,9 @@ class FlatOptimizer:
             buf = self._buf
             zero_grad = False
         flat_optimizer_step(self.params, self.m, self.v, self.step_ctr, buf, self.cfg, slope=self.slope,
-                            shadow=sh.buf if fresh else None, zero_grad=zero_grad, fused=fused,
-                            norm_out=self.grad_norm, norm_ws=self._norm_ws)
-        if fresh:
+                            shadow=(sh if self._fp8_shadow else sh.buf) if fresh else None, zero_grad=zero_grad,
+                            fused=fused, norm_out=self.grad_norm, norm_ws=self._norm_ws)
+        if fresh and not self._fp8_shadow:  # (flat_optimizer_step marks an FP8 shadow itself)
             sh.mark_fresh()
         return zero_grad
 

@@ -45,8 +45,12 @@ def run_ours(a, X, Y, dev, world):
     # --shadow: Adam also writes the bf16 weight operands (no per-forward casts). Measured
     # at W = 4096 / 2048 / 1024: 4.52 / 1.78 / 1.28 ms vs 4.56 / 1.75 / 1.28 casting each
     # forward (profiles/r3_shadow/), so the cast stays the default
-    opt = FlatOptimizer(bank.flat, bank.flat_grad, OptimConfig(lr=1e-3),
-                        shadow=bank.compute_shadow() if a.shadow else None)
+    # with --precision fp8-delayed, --shadow is the FP8 one: Adam writes the e4m3 weight operands
+    # (ops/fp8.py Fp8WeightShadow; profiles/fp8_shadow/)
+    shadow = None
+    if a.shadow:
+        shadow = bank.fp8_shadow() if a.precision == "fp8-delayed" else bank.compute_shadow()
+    opt = FlatOptimizer(bank.flat, bank.flat_grad, OptimConfig(lr=1e-3), shadow=shadow)
     mse = torch.nn.MSELoss()
     fwd = ddp if ddp is not None else bank
 
@@ -110,7 +114,8 @@ def main():
     ap.add_argument("--fp8_amax_history", type=int, default=16)
     ap.add_argument("--shadow", action="store_true",
                     help="ours: the Adam kernel writes the bf16 weight operands (ops/gemm.py ComputeShadow) "
-                         "instead of a cast before every forward")
+                         "instead of a cast before every forward; with --precision fp8-delayed the e4m3 ones "
+                         "(ops/fp8.py Fp8WeightShadow) instead of a quantiser launch per weight and forward")
     ap.add_argument("--gemm-backend", choices=["mfma", "blaslt"], default="mfma",
                     help="mfma: the library's kernels; blaslt: the large bf16 GEMMs on hipBLASLt + an epilogue "
                          "pass (scripts/blaslt_ref.py, an A/B reference outside the library)")
